@@ -11,14 +11,20 @@ mixture 0 is checked against tests/golden/input_sha256.json.  With --gpus N ever
 own ``--batch`` mixtures (configs[4]: 128 per GPU); there is no data-path collective, only the
 barrier and the max-over-ranks of the elapsed time.
 
-After the timed region, on rank 0 at N=1 (none of it is part of ``value``):
-  * a second loop over the same steps with HIP events around every kernel group -> ``roofline``;
-  * ``with_record_loss`` (the reference default), the AuxIVA-IP leg of the metric;
-  * ``configs``: BASELINE configs[1] literally (one mixture), configs[2] (AuxIVA-ISS, N=8,
-    F=2049, T=1024) and configs[3] (FastGaussMNMF, N=M=4, K=8), one mixture and a batch each,
-    every one with its own CPU baseline (the matching oracle class on this box's host cores).
+A plain run does only what the headline needs: set-up, ``--warmup`` steps, ONE timed region of
+exactly ``--steps`` steps, the ``--dump-outputs`` files if asked for, the result line.  With
+``--full``, after the timed region (none of it is part of ``value``):
+  * the timed region run five times back to back (``--repeats``), ``value`` the median region;
+  * a second loop over the same steps with HIP events around every kernel group -> ``roofline``,
+    with a live power / clock sample (rank 0 at N=1; every card while all ranks run at N>1);
+  * on rank 0 at N=1: ``cpu_baseline`` (the oracle on the host cores), ``with_record_loss`` (the
+    reference default), the AuxIVA-IP leg of the metric, ``configs``: BASELINE configs[1]
+    literally (one mixture), configs[2] (AuxIVA-ISS, N=8, F=2049, T=1024) and configs[3]
+    (FastGaussMNMF, N=M=4, K=8), one mixture and a batch each, every one with its own CPU
+    baseline, the pairwise / IPA legs and the end-to-end ``__call__`` legs.
 
-    python bench.py                       # 1 GPU, 128 mixtures, finishes in ~2-3 min
+    python bench.py --steps 20 --warmup 3 # 1 GPU, 128 mixtures, the headline line only
+    python bench.py --full                # everything above, finishes in ~40 s
     python bench.py --gpus 8              # starts 8 ranks itself (torch.distributed.run, RCCL)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 20 --warmup 3
@@ -48,16 +54,23 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every side measurement (repeated regions, roofline, "
+                         "power, CPU baselines, other configs, pairwise / IPA, end to end)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step computed (demix_filter, "
+                         "basis, activation of a seeded sample of the batch) as DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=None,
                     help="timed regions of exactly --steps steps each, run back to back; `value` is "
-                         "the MEDIAN region, all of them are listed (min / median / max)")
+                         "the MEDIAN region, all of them are listed (min / median / max); default "
+                         "1, 5 with --full")
     ap.add_argument("--batch", type=int, default=128, help="independent mixtures per GPU")
     ap.add_argument("--sources", type=int, default=4)
     ap.add_argument("--bins", type=int, default=1025)
     ap.add_argument("--frames", type=int, default=512)
     ap.add_argument("--basis", type=int, default=16)
     ap.add_argument("--power-seconds", type=float, default=2.5,
-                    help="length of the power / clock sampling leg (rank 0, N=1, not with --no-extra)")
+                    help="length of the power / clock sampling leg (--full; rank 0, N=1, not with --no-extra)")
     ap.add_argument("--e2e-mixtures", type=int, default=256,
                     help="host-resident mixtures of the pipelined end-to-end leg (0 = skip)")
     ap.add_argument("--e2e-sub-batch", type=int, default=64)
@@ -89,6 +102,24 @@ def make_separator(X, K, seed, record_loss=False):
     return sep
 
 
+DUMP_MIXTURES = 32  # 32 of the headline's 128 mixtures: 34 MB of .npy files
+
+
+def dump_outputs(sep, directory):
+    """What a caller of update_once() receives after the last timed step: the separator's
+    demix_filter, basis and activation (the fused IP1 call rewrites exactly these), for a fixed
+    seeded sample of DUMP_MIXTURES mixtures of the batch (all of them if the batch is smaller), in
+    float64; complex arrays get a trailing (real, imag) axis."""
+    os.makedirs(directory, exist_ok=True)
+    B = sep._X.shape[0]
+    pick = np.sort(np.random.default_rng(0).choice(B, size=min(B, DUMP_MIXTURES), replace=False))
+    for name in ("demix_filter", "basis", "activation"):
+        a = np.asarray(getattr(sep, name))[pick]
+        if np.iscomplexobj(a):
+            a = np.stack([a.real, a.imag], axis=-1)
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def settle_host():
     """A full collection of CPython's oldest generation walks every object torch and NumPy created at
     import (42 ms here) and lands in whichever short loop crosses the allocation threshold
@@ -100,7 +131,7 @@ def settle_host():
 
 def time_loop(fn, n, reps=3):
     """Seconds per call: the median of `reps` regions of exactly `n` calls each (the side legs only;
-    the headline has its own five regions).  One region was what rounds 1-5 timed, and a 20 ms leg
+    the headline has its own regions).  One region was what rounds 1-5 timed, and a 20 ms leg
     that starts right after seconds of host work (input generation, a pageable upload) caught the
     GPU's clocks on their way back up: configs[3] at 32 mixtures read 1.06 / 1.99 / 3.12 ms per
     iteration on three boxes of the same code while benchmarks/other_configs.py gave 1.08 each time."""
@@ -614,7 +645,7 @@ def main():
     if rank == 0 and (N, F, T) == tuple(pin["shape"]):
         sha_ok = x0_sha == pin["sha256"]
     X = torch.from_numpy(Xh).to(dev)
-    if not (rank == 0 and world == 1 and not args.no_extra):
+    if not (args.full and rank == 0 and world == 1 and not args.no_extra):
         del Xh  # (the end-to-end legs of the N = 1 run start from the host copy)
         Xh = None
     sep = make_separator(X, K, seed=2000 + rank)
@@ -629,14 +660,15 @@ def main():
         torch.cuda.synchronize()
 
     # ---- the timed region: exactly `steps` update_once() calls (one fused C-ABI call each),
-    # bracketed by barrier + synchronize on both sides.  It is run `--repeats` times back to back
-    # (round-3 verdict: a single 66 ms shot on a box whose clocks are still settling): every region is
-    # reported, `value` is the median one.
+    # bracketed by barrier + synchronize on both sides.  With --full it is run `--repeats` times back
+    # to back (round-3 verdict: a single 66 ms shot on a box whose clocks are still settling): every
+    # region is reported, `value` is the median one.
+    repeats = args.repeats if args.repeats is not None else (5 if args.full else 1)
     for _ in range(args.warmup):
         sep.update_once()
     settle_host()
     regions, own_regions = [], []
-    for _ in range(max(1, args.repeats)):
+    for _ in range(max(1, repeats)):
         fence()
         t0 = time.perf_counter()
         for _ in range(args.steps):
@@ -651,6 +683,8 @@ def main():
         own_regions.append(own)
     elapsed = float(np.median(regions))
     sep._check_device_errors()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(sep, args.dump_outputs)
 
     # ---- N > 1: what each rank did on its own, and the power of every card while all ranks run
     # (round-4 verdict item 10: the first real 8-GPU run should show at a glance whether a slow rank
@@ -663,7 +697,8 @@ def main():
                             device=dev if backend == "nccl" else torch.device("cpu"))
         gathered = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(gathered, mine)
-        joint_power = joint_power_leg(sep, min(args.power_seconds, 1.5), rank, fence)
+        if args.full:
+            joint_power = joint_power_leg(sep, min(args.power_seconds, 1.5), rank, fence)
         if rank == 0:
             rates = [B * args.steps / float(g.item()) for g in gathered]
             per_rank = {
@@ -680,64 +715,66 @@ def main():
             dist.destroy_process_group()
         return
 
-    # ---- second loop, same steps as separate kernel groups under HIP events -> roofline
-    avg_ms = kernel_group_events(sep, args.steps)
-    sep._check_device_errors()
-
     units = B * n_gpus * args.steps  # mixture-iterations
     value = units / elapsed
     pass_bytes = 16.0 * N * F * T * B  # one compulsory pass over the rank's X
-    dominant = max(("basis", "activation", "wcov"), key=lambda k: avg_ms[k])
-    achieved = pass_bytes / (avg_ms[dominant] * 1e-3) / 1e9
-    kernel_names = {"basis": "k_basis_fast", "activation": "k_activation_fast", "wcov": "k_wcov_fast"}
-    traffic = None
-    traffic_source = None
-    tpath = os.path.join(ROOT, "profiles", "roofline_traffic.json")
-    if os.path.exists(tpath):
-        try:
-            tj = json.load(open(tpath))
-            traffic = tj.get("k_ilrma_" + dominant, {}).get("hbm_bytes_per_launch_batch{}".format(B))
-            traffic_source = "profiles/roofline_traffic.json ({})".format(tj.get("_round", "r01"))
-            from ssspy_amd.utils.dataset import kernel_sources_sha256
-            if tj.get("_kernel_sources_sha256") not in (None, kernel_sources_sha256()):
-                # the counters were collected on other kernel sources: do not quote them
+    roofline = None
+    if args.full:
+        # ---- second loop, same steps as separate kernel groups under HIP events -> roofline
+        avg_ms = kernel_group_events(sep, args.steps)
+        sep._check_device_errors()
+
+        dominant = max(("basis", "activation", "wcov"), key=lambda k: avg_ms[k])
+        achieved = pass_bytes / (avg_ms[dominant] * 1e-3) / 1e9
+        kernel_names = {"basis": "k_basis_fast", "activation": "k_activation_fast", "wcov": "k_wcov_fast"}
+        traffic = None
+        traffic_source = None
+        tpath = os.path.join(ROOT, "profiles", "roofline_traffic.json")
+        if os.path.exists(tpath):
+            try:
+                tj = json.load(open(tpath))
+                traffic = tj.get("k_ilrma_" + dominant, {}).get("hbm_bytes_per_launch_batch{}".format(B))
+                traffic_source = "profiles/roofline_traffic.json ({})".format(tj.get("_round", "r01"))
+                from ssspy_amd.utils.dataset import kernel_sources_sha256
+                if tj.get("_kernel_sources_sha256") not in (None, kernel_sources_sha256()):
+                    # the counters were collected on other kernel sources: do not quote them
+                    traffic = None
+                    traffic_source += " -- stale: the pass kernels changed since it was collected"
+            except Exception:
                 traffic = None
-                traffic_source += " -- stale: the pass kernels changed since it was collected"
-        except Exception:
-            traffic = None
-    # fp64 work of a pass per (source, bin, frame): both NMF passes run GEMM1 (16 FMA on the matrix
-    # pipe), GEMM2 for num and den (32), y = W x (16), |y|^2 (2), the Newton reciprocal (5), the
-    # numerator factor (2) = 73 FMA = 146 flop (the SQ counters give 40.45 / 38.44 Gflop per launch at
-    # 128 mixtures against 39.2 from this count; the covariance pass counts 26.72: its figure is the
-    # counters', profiles/r03_pmc_sq_digest.md).
-    elems = float(N) * F * T * B
-    flop = {"basis": 146.0 * elems, "activation": 146.0 * elems, "wcov": 26.72e9 * elems / (4.0 * 1025 * 512 * 128)}
-    roofline = {
-        # the name rocprofv3 reports for this launch (tuned path of ilrma_fast.hip at these shapes)
-        # bound: what limits the pass.  Neither roof of the classic model is reached (frac / fp64_frac
-        # below): the passes run at the socket power cap with the shader clock throttled -- see
-        # "power" below (sampled live in this run) and profiles/r04_power_cap.md.  achieved / peak /
-        # frac stay on the HBM axis, as the contract asks.
-        "bound": "power", "kernel": kernel_names[dominant],
-        "achieved": round(achieved, 1),
-        "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-        "fp64_frac": round(flop[dominant] / (avg_ms[dominant] * 1e-3) / 1e12 / FP64_PEAK_TFLOPS, 4),
-        "traffic": traffic, "traffic_source": traffic_source,
-        "bytes_per_launch": pass_bytes, "avg_launch_ms": round(avg_ms[dominant], 4),
-        "per_kernel_ms": {k: round(v, 4) for k, v in avg_ms.items()},
-        "per_kernel_frac": {k: round(pass_bytes / (avg_ms[k] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-                            for k in ("basis", "activation", "wcov")},
-        "per_kernel_fp64_frac": {k: round(flop[k] / (avg_ms[k] * 1e-3) / 1e12 / FP64_PEAK_TFLOPS, 4)
-                                 for k in ("basis", "activation", "wcov")},
-        "measured": "HIP events around each kernel group in a second loop of the same steps "
-                    "(the timed region runs the fused update_once())",
-        "iteration_achieved": round(3 * pass_bytes / (elapsed / args.steps) / 1e9, 1),
-        "iteration_frac": round(3 * pass_bytes / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
-    }
-    if n_gpus == 1 and not args.no_extra:
-        roofline["power"] = power_leg(sep, args.power_seconds)
-    if joint_power is not None:
-        roofline["power_all_ranks"] = joint_power
+        # fp64 work of a pass per (source, bin, frame): both NMF passes run GEMM1 (16 FMA on the matrix
+        # pipe), GEMM2 for num and den (32), y = W x (16), |y|^2 (2), the Newton reciprocal (5), the
+        # numerator factor (2) = 73 FMA = 146 flop (the SQ counters give 40.45 / 38.44 Gflop per launch at
+        # 128 mixtures against 39.2 from this count; the covariance pass counts 26.72: its figure is the
+        # counters', profiles/r03_pmc_sq_digest.md).
+        elems = float(N) * F * T * B
+        flop = {"basis": 146.0 * elems, "activation": 146.0 * elems, "wcov": 26.72e9 * elems / (4.0 * 1025 * 512 * 128)}
+        roofline = {
+            # the name rocprofv3 reports for this launch (tuned path of ilrma_fast.hip at these shapes)
+            # bound: what limits the pass.  Neither roof of the classic model is reached (frac / fp64_frac
+            # below): the passes run at the socket power cap with the shader clock throttled -- see
+            # "power" below (sampled live in this run) and profiles/r04_power_cap.md.  achieved / peak /
+            # frac stay on the HBM axis, as the contract asks.
+            "bound": "power", "kernel": kernel_names[dominant],
+            "achieved": round(achieved, 1),
+            "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+            "fp64_frac": round(flop[dominant] / (avg_ms[dominant] * 1e-3) / 1e12 / FP64_PEAK_TFLOPS, 4),
+            "traffic": traffic, "traffic_source": traffic_source,
+            "bytes_per_launch": pass_bytes, "avg_launch_ms": round(avg_ms[dominant], 4),
+            "per_kernel_ms": {k: round(v, 4) for k, v in avg_ms.items()},
+            "per_kernel_frac": {k: round(pass_bytes / (avg_ms[k] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+                                for k in ("basis", "activation", "wcov")},
+            "per_kernel_fp64_frac": {k: round(flop[k] / (avg_ms[k] * 1e-3) / 1e12 / FP64_PEAK_TFLOPS, 4)
+                                     for k in ("basis", "activation", "wcov")},
+            "measured": "HIP events around each kernel group in a second loop of the same steps "
+                        "(the timed region runs the fused update_once())",
+            "iteration_achieved": round(3 * pass_bytes / (elapsed / args.steps) / 1e9, 1),
+            "iteration_frac": round(3 * pass_bytes / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
+        }
+        if n_gpus == 1 and not args.no_extra:
+            roofline["power"] = power_leg(sep, args.power_seconds)
+        if joint_power is not None:
+            roofline["power_all_ranks"] = joint_power
     out = {
         "metric": "GaussILRMA-IP1 update_once mixture-iterations/sec (F=1025,T=512,N=4,K=16)",
         "value": round(value, 2),
@@ -771,10 +808,11 @@ def main():
             "input": "nmf_mixture(seed=1000+b) per mixture b (SURVEY 8d)",
             "input_sha256_mixture0": x0_sha, "input_sha256_ok": sha_ok,
         },
-        "roofline": roofline,
     }
+    if roofline is not None:
+        out["roofline"] = roofline
 
-    extra = not args.no_extra and n_gpus == 1
+    extra = args.full and not args.no_extra and n_gpus == 1
     # ---- the same batch with record_loss=True semantics (SURVEY 8d asks for both): the separator's
     # own loop, update_once() then the loss bookkeeping of IterativeMethodBase
     if extra:
@@ -840,7 +878,7 @@ def main():
             torch.cuda.empty_cache()
 
     # ---- CPU baseline of the headline: the NumPy oracle (reference expression structure)
-    if not args.no_cpu_baseline and n_gpus == 1:
+    if args.full and not args.no_cpu_baseline and n_gpus == 1:
         from oracle.ilrma import GaussILRMAOracle
 
         def make():

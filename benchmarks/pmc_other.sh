@@ -24,7 +24,7 @@ run() {  # <workload> <command...>
     python benchmarks/pmc_summary.py $out/${name}_$p > $out/${name}_$p.json
   done
 }
-run ilrma_b128 python bench.py --batch 128 --steps 2 --warmup 1 --no-cpu-baseline --no-single
+run ilrma_b128 python bench.py --full --batch 128 --steps 2 --warmup 1 --no-cpu-baseline --no-single
 run iva_iss_b32 python benchmarks/other_configs.py --batch 32 --only iva_iss --iters 2
 run fastmnmf_b32 python benchmarks/other_configs.py --batch 32 --only fastmnmf --iters 2
 run gmnmf_b32 python benchmarks/other_configs.py --batch 32 --only gmnmf --iters 4

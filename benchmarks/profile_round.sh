@@ -13,13 +13,13 @@ out=$root/gpurun_out/$tag
 mkdir -p $out $out/legs
 cd /tmp && export TMPDIR=/tmp
 cd $root
-python bench.py > $out/bench.json 2> $out/bench.err
+python bench.py --full > $out/bench.json 2> $out/bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- \
-  python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-single > $out/stats.log 2>&1
+  python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-single > $out/stats.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/fetch -- \
-  python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-single > $out/fetch.log 2>&1
+  python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-single > $out/fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/write -- \
-  python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-single > $out/write.log 2>&1
+  python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-single > $out/write.log 2>&1
 python benchmarks/other_configs.py > $out/other_configs.txt 2>&1
 python benchmarks/other_configs.py --batch 32 >> $out/other_configs.txt 2>&1
 python benchmarks/other_configs.py --batch 128 --only fastmnmf --iters 10 >> $out/other_configs.txt 2>&1

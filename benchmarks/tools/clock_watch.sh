@@ -3,7 +3,7 @@
 #   benchmarks/tools/clock_watch.sh [steps]
 cd $GRAFT_REPO_ROOT
 steps=${1:-3000}
-python bench.py --no-cpu-baseline --no-single --steps $steps --warmup 5 > /tmp/bench_watch.log 2>&1 &
+python bench.py --full --no-cpu-baseline --no-single --steps $steps --warmup 5 > /tmp/bench_watch.log 2>&1 &
 pid=$!
 sleep 20   # import + input generation + upload
 for i in 1 2 3 4 5 6; do
