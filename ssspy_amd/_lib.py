@@ -198,3 +198,13 @@ def raise_if_singular(count, what):
     """Device kernels count singular per-bin systems; the reference raises LinAlgError."""
     if count:
         raise np.linalg.LinAlgError("Singular matrix ({} bin(s) in {})".format(int(count), what))
+
+
+def raise_if_barrier_timeouts():
+    """The fused IPA sweeps count the times a workgroup gave up waiting for its mixture's others
+    (ssspy_debug_barrier_timeouts); its vote was then partial."""
+    timeouts = load().ssspy_debug_barrier_timeouts()
+    if timeouts:
+        raise HipLibraryError(
+            "an IPA sweep gave up waiting for its mixture's workgroups {} time(s): the "
+            "results of this process are not to be trusted".format(timeouts))

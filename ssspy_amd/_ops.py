@@ -305,17 +305,16 @@ def ipa_sweep(Vc, normalization, max_iter, flooring, info=None, out=None, newton
     return out
 
 
-def update_by_ipa(Y, weight, kind, normalization, max_iter, flooring, info=None, not_converged=None,
-                  Vc=None, frame_power=False):
+def update_by_ipa(Y, weight, kind, normalization, max_iter, flooring, newton_ws, info=None,
+                  not_converged=None, Vc=None, frame_power=False):
     """One IPA sweep in place on the device spectrogram Y (B, N, F, T).  The weights are fixed over
     the sweep (ref: _update_spatial_model.py:436-445), so the covariances the reference recomputes
     from the updated spectrogram before every source step are G V G^H of the previous ones: one
     weighted covariance, the N steps on the per-bin statistics, one Y <- G Y (round 5; three passes
     over Y instead of 3 N).
     Vc: the weighted covariances of Y when the caller has formed them already (then `weight` is not
-    read; overwritten)."""
-    B, N = Y.shape[0], Y.shape[1]
-    newton_ws = dv.empty((int(_L().ssspy_ipa_sweep_newton_words(B, N)),), dv.i64, Y.device)
+    read; overwritten).  newton_ws: the sweep's vote words (bss._device_state.newton_words)."""
+    N = Y.shape[1]
     if Vc is None:
         Vc = weighted_covariance(Y, weight, kind, N)
     G = ipa_sweep(Vc, normalization, max_iter, flooring, info, newton_ws=newton_ws,

@@ -412,13 +412,9 @@ class DeviceStateMixin:
         return self._info_tensor()[1:]
 
     def _newton_words(self, dev):
-        """Vote words / arrival counters of the IPA sweeps (ssspy_ipa_sweep_newton_words), kept for
-        the call: every sweep prepares them itself."""
+        """Vote words / arrival counters of the IPA sweeps, kept for the call."""
         B, N = self._X.shape[0], self._X.shape[1]
-        words = self.__dict__.get("_newton_ws")
-        need = int(_lib.load().ssspy_ipa_sweep_newton_words(B, N))
-        if words is None or words.numel() < need or words.device != dev:
-            words = self.__dict__["_newton_ws"] = dv.empty((need,), dv.i64, dev)
+        words = self.__dict__["_newton_ws"] = newton_words(B, N, dev, self.__dict__.get("_newton_ws"))
         return words
 
     def _check_device_errors(self):
@@ -428,12 +424,8 @@ class DeviceStateMixin:
         info = self.__dict__.get("_info")
         if info is not None:
             singular, not_converged = (int(v) for v in info.tolist())  # synchronises
-            if self.__dict__.get("_newton_ws") is not None:
-                timeouts = _lib.load().ssspy_debug_barrier_timeouts()
-                if timeouts:
-                    raise _lib.HipLibraryError(
-                        "an IPA sweep gave up waiting for its mixture's workgroups {} time(s): the "
-                        "results of this process are not to be trusted".format(timeouts))
+            if self.__dict__.get("_newton_ws") is not None:  # (an IPA sweep ran)
+                _lib.raise_if_barrier_timeouts()
             if singular or not_converged:
                 info.zero_()
             if not_converged:
@@ -444,3 +436,101 @@ class DeviceStateMixin:
                         getattr(self, "newton_iter", "the given")), UserWarning)
             if singular:
                 _lib.raise_if_singular(singular, type(self).__name__)
+
+    # -- the loss ------------------------------------------------------------------------------
+    def _combine_loss(self, data, logdet, data2=None):
+        """data term (+ data2) - 2 sum_i log|det W_i| on the host, after the device-error check."""
+        self._check_device_errors()
+        values = dv.to_host(data)
+        if data2 is not None:
+            values = values + dv.to_host(data2)
+        return values - 2.0 * dv.to_host(logdet)
+
+    def _loss_entry(self, values):
+        """One ``loss`` entry from B values: a float, or a copied array for a batch."""
+        return values.copy() if self._batched else values[0].item()
+
+    def _host_loss(self, data, logdet):
+        return self._loss_entry(self._combine_loss(data, logdet))
+
+    def _unobserved_loss(self, n_iter) -> bool:
+        """Nothing can look at ``self.loss`` during the call: the terms may stay in HBM until its end."""
+        return self.record_loss and not self.callbacks and n_iter > 0
+
+    def _resident_loss(self, n_iter, initial_call, prepare) -> bool:
+        """The loop ``__call__`` runs with ``record_loss=True`` when nothing can look at the loss in
+        between (_unobserved_loss and the callers' own conditions): the terms of every state stay in
+        HBM, (n_iter + 1, B) each, and one download at the end assembles the list -- the wait for
+        two numbers per mixture after every iteration would drain the queue each time (round 6).
+        ``prepare(data, logdet)`` returns (step, end): ``step(t, record)`` runs iteration t and, when
+        ``record``, leaves the terms of the state it starts from in row t; ``end()`` leaves those of
+        the last state in row n_iter and may return a second data-term array (added on the host).
+        Row 0 only with ``initial_call``, as in the reference (ssspy/bss/base.py:68-77)."""
+        B, dev = self._X.shape[0], self._X.device
+        data = dv.zeros((n_iter + 1, B), dv.f64, dev)
+        logdet = dv.zeros((n_iter + 1, B), dv.f64, dev)
+        step, end = prepare(data, logdet)
+        for t in range(n_iter):
+            step(t, t > 0 or initial_call)
+        values = self._combine_loss(data, logdet, end())
+        self.loss.extend(self._loss_entry(v) for v in (values if initial_call else values[1:]))
+        return True
+
+    def _iterate_with_resident_terms(self, n_iter, initial_call) -> bool:
+        """_resident_loss around the plain ``update_once()``, the terms from ``_loss_terms``."""
+        def prepare(data, logdet):
+            def step(t, record):
+                if record:
+                    self._loss_terms(data[t], logdet[t])
+                self.update_once()
+
+            def end():
+                self._loss_terms(data[n_iter], logdet[n_iter])
+
+            return step, end
+        return self._resident_loss(n_iter, initial_call, prepare)
+
+
+def newton_words(B, N, dev, words=None):
+    """Vote words / arrival counters of the IPA sweeps (ssspy_ipa_sweep_newton_words): ``words`` if
+    large enough and on ``dev``, else fresh ones.  Every sweep prepares them itself."""
+    need = int(_lib.load().ssspy_ipa_sweep_newton_words(B, N))
+    if words is None or words.numel() < need or words.device != dev:
+        words = dv.empty((need,), dv.i64, dev)
+    return words
+
+
+class LossShares:
+    """Raw shares of one loss term for every state of a run in one zeroed (nslots, stride) array
+    (share s of entry e at s * stride + e, entry t * B + b for state t of mixture b), folded once at
+    the end -- instead of a memset, a counter memset and a fold launch per iteration (round 5).
+    With one share per entry the kernels write the finished term into ``terms`` itself."""
+
+    def __init__(self, nslots, n_states, B, dev, terms=None):
+        self.nslots, self.B, self.stride = nslots, B, n_states * B
+        self.terms, self.dev = terms, dev
+        self.slots = terms if nslots == 1 and terms is not None else dv.zeros(
+            (nslots, self.stride), dv.f64, dev)
+        self.flat = self.slots.reshape(-1)
+
+    @staticmethod
+    def fit(nslots, n_states, B) -> bool:
+        """Whether the shares of a run can be had: at most 256 MB, entries within int32."""
+        stride = n_states * B
+        return nslots == 1 or (nslots > 1 and stride < 2 ** 31 and nslots * stride * 8 <= (1 << 28))
+
+    def at(self, t):
+        """Where the shares of state t begin."""
+        return self.flat[t * self.B:]
+
+    def fold(self):
+        """The terms, (n_states, B): the shares summed in share order (into a fresh array when the
+        run was given none)."""
+        if self.slots is self.terms:
+            return self.terms
+        from .. import _ops
+
+        if self.terms is None:
+            self.terms = dv.zeros((self.stride // self.B, self.B), dv.f64, self.dev)
+        _ops.fold_scalar_slots(self.slots, self.stride, self.nslots, self.terms.reshape(-1))
+        return self.terms

@@ -14,6 +14,7 @@ from .. import _lib, _ops
 from ..special.flooring import max_flooring
 from ..utils.flooring import device_flooring
 from ..utils.select_pair import resolve_pairs, sequential_pair_selector
+from ._device_state import newton_words
 
 EPS = 1e-10
 _DEFAULT_FLOOR = functools.partial(max_flooring, eps=EPS)
@@ -171,9 +172,11 @@ def update_by_ipa(
         w = dv.to_device(np.broadcast_to(wt, (B, N, F, T)), dtype=np.float64)
         kind = _lib.WEIGHT_BIN_FRAME
     info = dv.zeros((2,), dv.i32)  # [singular systems, mixtures whose Newton loop did not converge]
-    _ops.update_by_ipa(Y, w, kind, normalization, max_iter, floor, info, not_converged=info[1:])
+    _ops.update_by_ipa(Y, w, kind, normalization, max_iter, floor, newton_words(B, N, Y.device),
+                       info, not_converged=info[1:])
     out = dv.to_host(Y)[0]
     singular, not_converged = (int(v) for v in info.tolist())
+    _lib.raise_if_barrier_timeouts()
     if not_converged:
         import warnings
 

@@ -24,7 +24,8 @@ from .. import _lib, _ops, _routes
 from ..special.flooring import identity, max_flooring
 from ..utils.flooring import choose_flooring_fn, device_flooring, host_floor, require_device_floor
 from ..utils.select_pair import resolve_pairs, sequential_pair_selector
-from ._device_state import DeviceStateMixin, Synced
+from ._device_state import LossShares, Synced
+from ._filter_base import _IP1, _IP2, _IPA, _ISS1, _ISS2, DemixingFilterBase
 from .base import IterativeMethodBase
 
 __all__ = ["GaussILRMA", "TILRMA", "GGDILRMA"]
@@ -33,20 +34,10 @@ spatial_algorithms = ["IP", "IP1", "IP2", "ISS", "ISS1", "ISS2", "IPA"]
 source_algorithms = ["MM", "ME"]
 EPS = 1e-10
 
-_IP1 = ("IP", "IP1")
-_ISS1 = ("ISS", "ISS1")
-_IP2 = ("IP2",)
-_ISS2 = ("ISS2",)
-_IPA = ("IPA",)
-_PROJECTION_BACK = ("projection_back",)
-_MDP = ("minimal_distortion_principle",)
 
-
-class ILRMABase(DeviceStateMixin, IterativeMethodBase):
+class ILRMABase(DemixingFilterBase):
     """State handling shared by the ILRMA variants (ref: ssspy/bss/ilrma.py:32-579)."""
 
-    demix_filter = Synced(dv.c128)
-    output = Synced(dv.c128)
     basis = Synced(dv.f64)
     activation = Synced(dv.f64)
     latent = Synced(dv.f64)
@@ -153,93 +144,6 @@ class ILRMABase(DeviceStateMixin, IterativeMethodBase):
                                     self._state_dev("latent"), self._Teff, self._Vrep)
         return self._Teff, self._Vrep
 
-    def _resolve_floor(self, flooring_fn):
-        if type(flooring_fn) is str and flooring_fn == "self":
-            return self._floor
-        return device_flooring(choose_flooring_fn(flooring_fn, method=self), allow_host=True)
-
-    def _uses_filter(self) -> bool:
-        return not self._state_is_none("demix_filter")
-
-    def _implied_filter(self):
-        return None
-
-    # -- scale restoration ------------------------------------------------------------------
-    def restore_scale(self) -> None:
-        """ref: ssspy/bss/ilrma.py:538-555."""
-        scale_restoration = self.scale_restoration
-        assert scale_restoration, "Set self.scale_restoration=True."
-        if type(scale_restoration) is bool:
-            scale_restoration = _PROJECTION_BACK[0]
-        if scale_restoration in _PROJECTION_BACK:
-            self.apply_projection_back()
-        elif scale_restoration in _MDP:
-            self.apply_minimal_distortion_principle()
-        else:
-            raise ValueError("{} is not supported for scale restoration.".format(scale_restoration))
-
-    def apply_projection_back(self) -> None:
-        """ref: ssspy/bss/ilrma.py:557-565, :1969-1979; algorithm/projection_back.py:87-121."""
-        assert self.scale_restoration, "Set self.scale_restoration=True."
-        info = self._info_tensor()
-        if self._uses_filter():
-            W = self._state_dev("demix_filter")
-            _ops.projection_back_filter(W, self.reference_id, info)
-            self._state_touch("demix_filter")
-            self._state_set_dev("output", _ops.separate(self._X, W))
-        elif self._implied_filter() is not None and self.reference_id is not None:
-            # the same scales from the filters the output state implies: one pass instead of four
-            W = self._implied_filter().clone()
-            _ops.projection_back_filter(W, self.reference_id, info)
-            self._state_set_dev("output", _ops.separate(self._X, W))
-            self._implied = (W, self._state_rev("output"))
-        else:
-            Y = self._state_dev("output")
-            XY = _ops.cross_covariance(self._X, Y)
-            YY = _ops.cross_covariance(Y, Y)
-            G = _ops.projection_back_scale(XY, YY, self.reference_id, info)
-            _ops.separate(Y, G, out=Y)
-            self._state_touch("output")
-
-    def apply_minimal_distortion_principle(self) -> None:
-        """Per (bin, source) scale z = <y, x_ref> / <y, y>, output conj(z) y; with a filter state the
-        filter is re-fitted as Y X^H (X X^H)^-1 like the reference.
-        ref: ssspy/bss/ilrma.py:567-579, :1981-1989; algorithm/minimal_distortion_principle.py:6-43."""
-        assert self.scale_restoration, "Set self.scale_restoration=True."
-        filt = self._uses_filter()
-        if self.reference_id is None:
-            # reachable only by clearing the attribute after construction; as in the reference the
-            # estimate gains a leading channel axis (minimal_distortion_principle.py:34-35) and a
-            # filter state cannot take that shape
-            if filt:
-                raise ValueError("reference_id=None needs the output state (ISS / IPA), not filters.")
-            from ..algorithm import minimal_distortion_principle as _mdp
-
-            Y, X = dv.to_host(self._state_dev("output")), dv.to_host(self._X)
-            out = np.stack([_mdp(y, reference=x, reference_id=None) for y, x in zip(Y, X)])
-            self.output = out if self._batched else out[0]
-            return
-        if filt:
-            Y = _ops.separate(self._X, self._state_dev("demix_filter"))
-        else:
-            Y = self._state_dev("output")
-        G = _ops.mdp_scale(_ops.cross_covariance(Y, self._X), _ops.cross_covariance(Y, Y),
-                           self.reference_id)
-        _ops.separate(Y, G, out=Y)
-        if filt:
-            W = _ops.demix_from_covariance(_ops.cross_covariance(Y, self._X), self._C(),
-                                           self._info_tensor())
-            self._state_set_dev("demix_filter", W)
-            self._state_set_dev("output", Y)
-        else:
-            self._state_touch("output")
-
-    def _host_loss(self, data, logdet_sum):
-        """loss = data term - 2 sum_i log|det W_i|, combined on the host (B numbers each)."""
-        self._check_device_errors()
-        values = dv.to_host(data) - 2.0 * dv.to_host(logdet_sum)
-        return values.copy() if self._batched else values[0].item()
-
 
 class _MMILRMA(ILRMABase):
     """Everything the three source models share: the iteration, the MM updates, the spatial
@@ -286,14 +190,12 @@ class _MMILRMA(ILRMABase):
         """
         self._bind_input(input)
         self._reset(flooring_fn=self.flooring_fn, **kwargs)
-        if not (self._iterate_with_deferred_loss(int(n_iter), initial_call)
-                or self._iterate_with_resident_terms(int(n_iter), initial_call)):
+        n_iter = int(n_iter)
+        if not (self._iterate_with_deferred_loss(n_iter, initial_call)
+                or (self._stock_loss_loop(n_iter)
+                    and self._iterate_with_resident_terms(n_iter, initial_call))):
             IterativeMethodBase.__call__(self, n_iter=n_iter, initial_call=initial_call)
-        if self.scale_restoration:
-            self.restore_scale()
-        if self._uses_filter():
-            self._state_set_dev("output", _ops.separate(self._X, self._state_dev("demix_filter")))
-        return self._final_output()
+        return self._finish_call()
 
     def __repr__(self) -> str:
         s = "{}(n_basis={}{}, spatial_algorithm={}, source_algorithm={}, domain={}".format(
@@ -314,41 +216,17 @@ class _MMILRMA(ILRMABase):
         """ref: ssspy/bss/ilrma.py:875-898."""
         flooring_fn = choose_flooring_fn(flooring_fn, method=self)
         super()._reset(flooring_fn=flooring_fn, **kwargs)
-        self._logdet_cache = None
-        self._implied = None
-        self._amp_reset()
-        if (self.spatial_algorithm in ["ISS", "ISS1", "ISS2", "IPA"] and self._X.shape[1] <= 4
-                and self._base_model[0] == _lib.SOURCE_GAUSS):
-            # the filters the output state implies (output = W x), kept next to it: see
-            # _update_spatial_model_implied().  Up to 4 sources, where the passes over (X, W) are
-            # the tuned IP1 ones (8 sources, 16 mixtures: ISS2 4.0 against 2.9 ms on Y); Gauss model
-            # only: W U W^H rounds like eps |W|^2 |U| where the direct sum rounds like eps |y|^2, and
-            # the t / GGD weights 1 / |y|^(2 - beta) feed that back (the GGD ISS2 golden: 4e-10 on Y,
-            # 4e-7 through the filters after 10 iterations -- both started from 1e-15 at iteration 2).
-            # How far the product can round is measured by every launch that forms it and the route
-            # is left where that passes its bound (_amp_exceeded; rounds 5's fence of 16 frames per
-            # source is gone: the draw it was fitted to -- 11 frames for 4 sources, 1e-7 of the
-            # oracle after 8 ISS2 iterations through the filters -- now leaves after the second)
-            self._implied = (self._state_dev("demix_filter").clone(), self._state_rev("output"))
-        if self.spatial_algorithm in ["ISS", "ISS1", "ISS2", "IPA"] and not self.record_loss:
-            self.demix_filter = None  # (nothing reads the log-determinant: no tracker)
-        elif self.spatial_algorithm in ["ISS", "ISS1", "ISS2", "IPA"]:
-            # sum_i log|det W_i| of the filters the ISS state stops carrying, as (tensor, revision of
-            # `output` it describes); the fused sweep and the power normalisation move it along, so
-            # compute_loss() need not rebuild W from Y X^H (see AuxIVA._reset)
-            self._logdet_cache = (_ops.sum_logdet(self._state_dev("demix_filter")),
-                                  self._state_rev("output"))
-            self.demix_filter = None
+        self._reset_output_state()
 
-    def _tracked_logdet(self):
-        """The tracked sum_i log|det W_i| if it describes the current output, else None."""
-        cache = getattr(self, "_logdet_cache", None)
-        if cache is not None and cache[1] == self._state_rev("output"):
-            return cache[0]
-        return None
-
-    def _restamp_logdet(self, tracked) -> None:
-        self._logdet_cache = None if tracked is None else (tracked, self._state_rev("output"))
+    def _implied_route_wanted(self) -> bool:
+        # Gauss model only: W U W^H rounds like eps |W|^2 |U| where the direct sum rounds like
+        # eps |y|^2, and the t / GGD weights 1 / |y|^(2 - beta) feed that back (the GGD ISS2 golden:
+        # 4e-10 on Y, 4e-7 through the filters after 10 iterations -- both started from 1e-15 at
+        # iteration 2).  Round 5's fence of 16 frames per source is gone: the draw it was fitted to
+        # (11 frames for 4 sources, 1e-7 of the oracle after 8 ISS2 iterations through the filters)
+        # now leaves the route after the second (_amp_exceeded)
+        return (self.spatial_algorithm in _ISS1 + _ISS2 + _IPA
+                and self._base_model[0] == _lib.SOURCE_GAUSS)
 
     # -- the loop with the loss as a by-product ----------------------------------------------
     def _fused_ip1(self) -> bool:
@@ -367,92 +245,60 @@ class _MMILRMA(ILRMABase):
         at ``self.loss`` in between: no callbacks, and ``update_once`` / ``compute_loss`` not
         overridden.  Otherwise (returns False) the reference's loop order runs unchanged.
         ref: ssspy/bss/base.py:68-77, ssspy/bss/ilrma.py:1910-1967."""
-        cls = type(self)
-        if not (self.record_loss and not self.callbacks and n_iter > 0 and self._fused_ip1()
-                and host_floor(self._floor) is None
-                and cls.update_once is _MMILRMA.update_once
-                and cls.compute_loss is _MMILRMA.compute_loss):
+        if not (self._stock_loss_loop(n_iter) and self._fused_ip1()
+                and host_floor(self._floor) is None):
             return False
         B, N, F, T = self._X.shape
-        dev = self._X.device
-        if not _ops.ilrma_deferred_loss_supported(N, F, T, self.n_basis, float(self.domain), self._model):
+        K, p = self.n_basis, float(self.domain)
+        if not _ops.ilrma_deferred_loss_supported(N, F, T, K, p, self._model):
             return False  # shapes / models outside the tuned kernels have no such by-product
         if self._U is None:
-            self._U = dv.empty((B, F, N, N, N), dv.c128, dev)
-        data = dv.zeros((n_iter + 1, B), dv.f64, dev)
-        logdet = dv.zeros((n_iter + 1, B), dv.f64, dev)
-        C = self._C() if self.normalization else None
-        W, Tb, Vb = (self._state_dev(k) for k in ("demix_filter", "basis", "activation"))
-        args = (self._X, C, W, Tb, Vb, self._U, float(self.domain), bool(self.normalization),
-                self._floor, self._ws, self._ws_bytes, self._info_tensor())
-        # the data terms of all iterations as raw per-wave shares in ONE zeroed array, folded once at
-        # the end (round 5: a memset, a counter memset and a fold launch per iteration before)
-        nslots = _ops.ilrma_deferred_loss_slots(B, N, F, T, self.n_basis, float(self.domain),
-                                                self._model)
-        stride = (n_iter + 1) * B
-        slots = None
-        if nslots and stride < 2 ** 31 and nslots * stride * 8 <= (1 << 28):  # (<= 256 MB)
-            slots = dv.zeros((nslots, stride), dv.f64, dev)
-        flat = slots.reshape(-1) if slots is not None else None
-        # the log-determinants the same way (round 6): one share per mixture (the finished sum) or,
-        # for a handful of mixtures, one per 16-bin tile of the IP1 kernel, folded at the end
-        nld = _ops.ilrma_deferred_logdet_slots(B, N, F, T, self.n_basis, float(self.domain),
-                                               self._model) if slots is not None else 1
-        ld = dv.zeros((nld, stride), dv.f64, dev) if nld > 1 else logdet
-        ld_flat = ld.reshape(-1)
-        for t in range(n_iter):
-            if t == 0 and not initial_call:
-                # the reference records nothing before the first iteration in this case
-                _ops.ilrma_ip1_update(*args, model=self._model)
-            elif slots is not None:
-                _ops.ilrma_ip1_update_loss_slots(*args, flat[t * B:], stride, ld_flat[t * B:],
-                                                 model=self._model)
-            elif not _ops.ilrma_ip1_update_deferred_loss(*args, data[t], logdet[t],
-                                                         model=self._model):
-                raise RuntimeError("deferred loss unavailable although reported as supported")
-        if slots is not None:
-            _ops.fold_scalar_slots(slots, stride, nslots, data.reshape(-1))
-            if nld > 1:
-                _ops.fold_scalar_slots(ld, stride, nld, logdet.reshape(-1))
-        for name in ("demix_filter", "basis", "activation"):
-            self._state_touch(name)
-        _ops.ilrma_loss_data(self._X, W, Tb, Vb, float(self.domain), out=data[n_iter],
-                             model=self._model)
-        _ops.sum_logdet(W, out=logdet[n_iter])
-        self._check_device_errors()
-        values = dv.to_host(data) - 2.0 * dv.to_host(logdet)
-        if not initial_call:
-            values = values[1:]
-        self.loss.extend(v.copy() if self._batched else v[0].item() for v in values)
-        return True
+            self._U = dv.empty((B, F, N, N, N), dv.c128, self._X.device)
 
-    def _iterate_with_resident_terms(self, n_iter: int, initial_call: bool) -> bool:
-        """``record_loss=True`` for every iteration the deferred form above does not serve (ISS /
-        ISS2 / IP2 / IPA, heavy-tailed models, ...) without a host round trip per iteration
-        (round 6): ``compute_loss()`` downloads two numbers per mixture and the wait for them
-        drains the queue after every iteration.  Here the terms stay in HBM and one download at
-        the end assembles the list.  Only with the library's own ``update_once`` /
-        ``compute_loss`` and no callbacks; otherwise (returns False) the reference's loop runs
-        unchanged.  ref: ssspy/bss/base.py:68-77, ssspy/bss/ilrma.py:1910-1967."""
+        def prepare(data, logdet):
+            C = self._C() if self.normalization else None
+            W, Tb, Vb = (self._state_dev(k) for k in ("demix_filter", "basis", "activation"))
+            args = (self._X, C, W, Tb, Vb, self._U, p, bool(self.normalization), self._floor,
+                    self._ws, self._ws_bytes, self._info_tensor())
+            # the data terms of all iterations as raw per-wave shares, and the log-determinants the
+            # same way (round 6): one share per mixture (the finished sum) or, for a handful of
+            # mixtures, one per 16-bin tile of the IP1 kernel
+            nslots = _ops.ilrma_deferred_loss_slots(B, N, F, T, K, p, self._model)
+            shares = None
+            if nslots and LossShares.fit(nslots, n_iter + 1, B):
+                nld = _ops.ilrma_deferred_logdet_slots(B, N, F, T, K, p, self._model)
+                if LossShares.fit(nld, n_iter + 1, B):
+                    shares = (LossShares(nslots, n_iter + 1, B, self._X.device, data),
+                              LossShares(nld, n_iter + 1, B, self._X.device, logdet))
+
+            def step(t, record):
+                if not record:  # (the reference records nothing before the first iteration)
+                    _ops.ilrma_ip1_update(*args, model=self._model)
+                elif shares is not None:
+                    _ops.ilrma_ip1_update_loss_slots(*args, shares[0].at(t), shares[0].stride,
+                                                     shares[1].at(t), model=self._model)
+                elif not _ops.ilrma_ip1_update_deferred_loss(*args, data[t], logdet[t],
+                                                             model=self._model):
+                    raise RuntimeError("deferred loss unavailable although reported as supported")
+
+            def end():
+                for sh in shares or ():
+                    sh.fold()
+                for name in ("demix_filter", "basis", "activation"):
+                    self._state_touch(name)
+                _ops.ilrma_loss_data(self._X, W, Tb, Vb, p, out=data[n_iter], model=self._model)
+                _ops.sum_logdet(W, out=logdet[n_iter])
+
+            return step, end
+        return self._resident_loss(n_iter, initial_call, prepare)
+
+    def _stock_loss_loop(self, n_iter: int) -> bool:
+        """_iterate_with_resident_terms serves every iteration the deferred form above does not
+        (ISS / ISS2 / IP2 / IPA, heavy-tailed models, ...) with the library's own ``update_once`` /
+        ``compute_loss``.  ref: ssspy/bss/ilrma.py:1910-1967."""
         cls = type(self)
-        if not (self.record_loss and not self.callbacks and n_iter > 0
-                and cls.update_once is _MMILRMA.update_once
-                and cls.compute_loss is _MMILRMA.compute_loss):
-            return False
-        B, dev = self._X.shape[0], self._X.device
-        data = dv.zeros((n_iter + 1, B), dv.f64, dev)
-        logdet = dv.zeros((n_iter + 1, B), dv.f64, dev)
-        for t in range(n_iter + 1):
-            if t > 0 or initial_call:
-                self._loss_terms(data[t], logdet[t])
-            if t < n_iter:
-                self.update_once()
-        self._check_device_errors()
-        values = dv.to_host(data) - 2.0 * dv.to_host(logdet)
-        if not initial_call:
-            values = values[1:]
-        self.loss.extend(v.copy() if self._batched else v[0].item() for v in values)
-        return True
+        return (self._unobserved_loss(n_iter) and cls.update_once is _MMILRMA.update_once
+                and cls.compute_loss is _MMILRMA.compute_loss)
 
     # -- one iteration -----------------------------------------------------------------------
     def _is_stock(self) -> bool:
@@ -539,30 +385,10 @@ class _MMILRMA(ILRMABase):
         if self.spatial_algorithm in _IPA:
             require_device_floor(floor, "IPA")
         Y = self._state_dev("output")
-        B, N, F, T = Y.shape
-        Vc = self._output_statistics(Y, flooring_fn)
-        if Vc is None:
-            if self._ggd_host_floor(flooring_fn):
-                varphi = self._ggd_weights_host_floor(Y, floor)
-            else:
-                varphi = _ops.ilrma_iss_weight(*self._nmf_pair(), float(self.domain), Y=Y,
-                                               model=self._model, flooring=floor)
-            Vc = _ops.weighted_covariance(Y, varphi, _lib.WEIGHT_BIN_FRAME, N)
-        if self.spatial_algorithm in _ISS1:
-            G = _ops.iss1_transform(Vc, floor)
-        elif self.spatial_algorithm in _ISS2:
-            G = _ops.iss2_transform(Vc, resolve_pairs(getattr(self, "pair_selector", None), N),
-                                    floor, self._info_tensor())
-        else:
-            G = _ops.ipa_sweep(Vc, self.lqpqm_normalization, self.newton_iter, floor,
-                               self._info_tensor(), newton_ws=self._newton_words(Y.device),
-                               not_converged=self._newton_counter())
+        G = self._spatial_transform(self._iss_statistics(Y, flooring_fn), floor)
         C = self._output_covariance(Y)
-        _ops.ilrma_normalize_filter(G, C, self._state_dev("basis"), float(self.domain), floor,
-                                    self._ws, self._ws_bytes)
-        spare = getattr(self, "_ycov_spare", None)
-        if spare is None or spare.shape != C.shape or spare.data_ptr() == C.data_ptr():
-            spare = dv.empty(tuple(C.shape), dv.c128, Y.device)
+        self._normalize_filter(G, C, floor)
+        spare = self._spare("_ycov_spare", C)
         _ops.covariance_congruence(C, G, spare)
         tracked = self._tracked_logdet()
         if tracked is not None:
@@ -573,27 +399,12 @@ class _MMILRMA(ILRMABase):
         self._ycov, self._ycov_spare = (spare, self._state_rev("output")), C
         self._restamp_logdet(tracked)
 
+    def _normalize_filter(self, W, C, floor) -> None:
+        """Rows of W / psi_n, basis / psi_n^p with psi_n^2 = mean_i w_n^H C_i w_n."""
+        _ops.ilrma_normalize_filter(W, C, self._state_dev("basis"), float(self.domain), floor,
+                                    self._ws, self._ws_bytes)
+
     # -- ISS / ISS2 / IPA read through the filters their updates imply (round 5) ---------------------
-    def _implied_filter(self):
-        """W with output = W x while nothing else rewrote ``output`` since, else None."""
-        kept = getattr(self, "_implied", None)
-        if (kept is None or kept[1] != self._state_rev("output")
-                or not _routes.get("implied_filter")):
-            return None
-        return kept[0]
-
-    def _fill_output_from_implied_filter(self) -> None:
-        W = self._implied[0]
-        _ops.separate(self._X, W, out=self._state()["output"]["dev"])
-
-    def _leave_implied_route(self) -> None:
-        """Form Y = W x now and go on with the iterations that rewrite it (the reference's)."""
-        W = self._implied[0]
-        self._state_dev("output")  # (runs the deferred fill)
-        if getattr(self, "_logdet_cache", None) is not None:  # (the on-Y updates move it along)
-            self._logdet_cache = (_ops.sum_logdet(W), self._state_rev("output"))
-        self._implied = None
-
     def _update_spatial_model_implied(self, flooring_fn) -> None:
         """update_spatial_model() + normalize() of the ISS / ISS2 / IPA iterations without touching Y.
         The reference keeps only the separated spectrogram and rewrites it, y <- G y
@@ -609,37 +420,13 @@ class _MMILRMA(ILRMABase):
         if self._amp_exceeded():
             self._leave_implied_route()
             return self._update_spatial_model_folded(flooring_fn)
-        W = self._implied_filter()
-        B, N, F, T = self._X.shape
-        dev = self._X.device
-        if self._U is None:
-            self._U = dv.empty((B, F, N, N, N), dv.c128, dev)
-        if getattr(self, "_Vc", None) is None or tuple(self._Vc.shape) != (B, F, N, N, N):
-            self._Vc = dv.empty((B, F, N, N, N), dv.c128, dev)
-        _ops.ilrma_weighted_covariance(self._X, *self._nmf_pair(), float(self.domain), self._ws,
-                                       self._ws_bytes, out=self._U, W=W, model=self._model,
-                                       flooring=floor)
-        tracked = self._amp_tracked(self._C())
-        Vc = _ops.covariance_congruence(self._U, W, self._Vc, tracked=tracked)
-        self._amp_launched(tracked)
-        if self.spatial_algorithm in _ISS1:
-            G = _ops.iss1_transform(Vc, floor)
-        elif self.spatial_algorithm in _ISS2:
-            G = _ops.iss2_transform(Vc, resolve_pairs(getattr(self, "pair_selector", None), N),
-                                    floor, self._info_tensor())
-        else:
-            G = _ops.ipa_sweep(Vc, self.lqpqm_normalization, self.newton_iter, floor,
-                               self._info_tensor(), newton_ws=self._newton_words(dev),
-                               not_converged=self._newton_counter())
-        spare = getattr(self, "_implied_spare", None)
-        if spare is None or spare.shape != W.shape or spare.data_ptr() == W.data_ptr():
-            spare = dv.empty(tuple(W.shape), dv.c128, dev)
-        _ops.compose_filters(G, W, spare)
-        _ops.ilrma_normalize_filter(spare, self._C(), self._state_dev("basis"), float(self.domain),
-                                    floor, self._ws, self._ws_bytes)
-        self._state_touch("basis")
-        self._state_defer("output", self._fill_output_from_implied_filter)
-        self._implied, self._implied_spare = (spare, self._state_rev("output")), W
+        self._filter_covariance(self._implied_filter(), floor)
+
+        def normalize(W):
+            self._normalize_filter(W, self._C(), floor)
+            self._state_touch("basis")
+
+        self._implied_step(self._U, floor, normalize)
 
     def _power_normalization_or_off(self) -> bool:
         return (not self.normalization) or type(self.normalization) is bool \
@@ -767,17 +554,17 @@ class _MMILRMA(ILRMABase):
         """Iterative projection with adjustment on per-bin statistics: per source, weighted
         covariance of the current output, LQPQM update matrix, Y <- G Y.
         ref: ssspy/bss/ilrma.py:1794-1908."""
-        require_device_floor(self._resolve_floor(flooring_fn), "IPA")
+        floor = self._resolve_floor(flooring_fn)
+        require_device_floor(floor, "IPA")
         Y = self._state_dev("output")
         Vc = self._output_statistics(Y, flooring_fn)
         varphi = None
         if Vc is None:
             varphi = _ops.ilrma_iss_weight(*self._nmf_pair(), float(self.domain), Y=Y,
-                                           model=self._model,
-                                           flooring=self._resolve_floor(flooring_fn))
+                                           model=self._model, flooring=floor)
         _ops.update_by_ipa(Y, varphi, _lib.WEIGHT_BIN_FRAME, self.lqpqm_normalization,
-                           self.newton_iter, self._resolve_floor(flooring_fn), self._info_tensor(),
-                           not_converged=self._newton_counter(), Vc=Vc)
+                           self.newton_iter, floor, self._newton_words(Y.device),
+                           self._info_tensor(), not_converged=self._newton_counter(), Vc=Vc)
         self._state_touch("output")
 
     def _output_statistics(self, Y, flooring_fn):
@@ -808,6 +595,34 @@ class _MMILRMA(ILRMABase):
                                        flooring=floor)
         return self._Vc
 
+    def _iss_statistics(self, Y, flooring_fn):
+        """The per-bin statistics of the ISS / ISS2 / IPA steps on Y: _output_statistics, else
+        the weights (a host floor on GGD's) and the generic weighted covariance."""
+        Vc = self._output_statistics(Y, flooring_fn)
+        if Vc is not None:
+            return Vc
+        floor = self._resolve_floor(flooring_fn)
+        if self._ggd_host_floor(flooring_fn):
+            varphi = self._ggd_weights_host_floor(Y, floor)
+        else:
+            varphi = _ops.ilrma_iss_weight(*self._nmf_pair(), float(self.domain), Y=Y,
+                                           model=self._model, flooring=floor)
+        return _ops.weighted_covariance(Y, varphi, _lib.WEIGHT_BIN_FRAME, Y.shape[1])
+
+    def _filter_covariance(self, W, floor) -> None:
+        """U_n = mean_j varphi_nij x x^H of the mixture into ``self._U`` for the filter updates
+        (IP1 / IP2) and the implied route; with a host floor on GGD's weights from Y = W x."""
+        B, N, F, T = self._X.shape
+        if host_floor(floor) is not None and self._base_model[0] == _lib.SOURCE_GGD:
+            varphi = self._ggd_weights_host_floor(_ops.separate(self._X, W), floor)
+            self._U = _ops.weighted_covariance(self._X, varphi, _lib.WEIGHT_BIN_FRAME, N)
+            return
+        if self._U is None:
+            self._U = dv.empty((B, F, N, N, N), dv.c128, self._X.device)
+        _ops.ilrma_weighted_covariance(self._X, *self._nmf_pair(), float(self.domain), self._ws,
+                                       self._ws_bytes, out=self._U, W=W, model=self._model,
+                                       flooring=floor)
+
     def _ggd_weights_host_floor(self, Y, floor):
         """varphi (B, N, F, T) of the GGD model for a flooring callable the kernels do not know
         (round 6).  The reference floors q = |y|^(2 - beta) per element before it forms
@@ -834,57 +649,27 @@ class _MMILRMA(ILRMABase):
         """Weighted covariance + pairwise iterative projection.  ref: ssspy/bss/ilrma.py:1509-1633."""
         # (the t model's weights hold no floor, ssspy/bss/ilrma.py:2915-2935; GGD's floor
         #  |y|^(2 - beta) per element, :3987-4011: a callable goes through _ggd_weights_host_floor)
-        B, N, F, T = self._X.shape
-        if self._ggd_host_floor(flooring_fn):
-            Y = _ops.separate(self._X, self._state_dev("demix_filter"))
-            varphi = self._ggd_weights_host_floor(Y, self._resolve_floor(flooring_fn))
-            self._U = _ops.weighted_covariance(self._X, varphi, _lib.WEIGHT_BIN_FRAME, N)
-        else:
-            if self._U is None:
-                self._U = dv.empty((B, F, N, N, N), dv.c128, self._X.device)
-            _ops.ilrma_weighted_covariance(self._X, *self._nmf_pair(), float(self.domain),
-                                           self._ws, self._ws_bytes, out=self._U,
-                                           W=self._state_dev("demix_filter"), model=self._model,
-                                           flooring=self._resolve_floor(flooring_fn))
+        floor = self._resolve_floor(flooring_fn)
+        self._filter_covariance(self._state_dev("demix_filter"), floor)
         _ops.update_by_ip2(self._state_dev("demix_filter"), self._U,
-                           resolve_pairs(getattr(self, "pair_selector", None), N),
-                           self._resolve_floor(flooring_fn), self._info_tensor())
+                           resolve_pairs(getattr(self, "pair_selector", None), self._X.shape[1]),
+                           floor, self._info_tensor())
         self._state_touch("demix_filter")
 
     def update_spatial_model_iss2(self, flooring_fn="self") -> None:
         """Pairwise iterative source steering on per-bin statistics.  ref: ilrma.py:1698-1792."""
         Y = self._state_dev("output")
-        N = Y.shape[1]
-        Vc = self._output_statistics(Y, flooring_fn)
-        if Vc is None:
-            if self._ggd_host_floor(flooring_fn):
-                varphi = self._ggd_weights_host_floor(Y, self._resolve_floor(flooring_fn))
-            else:
-                varphi = _ops.ilrma_iss_weight(*self._nmf_pair(), float(self.domain), Y=Y,
-                                               model=self._model,
-                                               flooring=self._resolve_floor(flooring_fn))
-            Vc = _ops.weighted_covariance(Y, varphi, _lib.WEIGHT_BIN_FRAME, N)
-        G = _ops.iss2_transform(Vc, resolve_pairs(getattr(self, "pair_selector", None), N),
+        G = _ops.iss2_transform(self._iss_statistics(Y, flooring_fn),
+                                resolve_pairs(getattr(self, "pair_selector", None), Y.shape[1]),
                                 self._resolve_floor(flooring_fn), self._info_tensor())
         _ops.separate(Y, G, out=Y)
         self._state_touch("output")
 
     def update_spatial_model_ip1(self, flooring_fn="self") -> None:
         """Weighted covariance + iterative projection.  ref: ssspy/bss/ilrma.py:1440-1507."""
-        B, N, F, T = self._X.shape
-        if self._ggd_host_floor(flooring_fn):  # (its weights floor |y|^(2 - beta) per element)
-            Y = _ops.separate(self._X, self._state_dev("demix_filter"))
-            varphi = self._ggd_weights_host_floor(Y, self._resolve_floor(flooring_fn))
-            self._U = _ops.weighted_covariance(self._X, varphi, _lib.WEIGHT_BIN_FRAME, N)
-        else:
-            if self._U is None:
-                self._U = dv.empty((B, F, N, N, N), dv.c128, self._X.device)
-            _ops.ilrma_weighted_covariance(self._X, *self._nmf_pair(), float(self.domain),
-                                           self._ws, self._ws_bytes, out=self._U,
-                                           W=self._state_dev("demix_filter"), model=self._model,
-                                           flooring=self._resolve_floor(flooring_fn))
-        _ops.update_by_ip1(self._state_dev("demix_filter"), self._U,
-                           self._resolve_floor(flooring_fn), self._info_tensor())
+        floor = self._resolve_floor(flooring_fn)
+        self._filter_covariance(self._state_dev("demix_filter"), floor)
+        _ops.update_by_ip1(self._state_dev("demix_filter"), self._U, floor, self._info_tensor())
         self._state_touch("demix_filter")
 
     def update_spatial_model_iss1(self, flooring_fn="self") -> None:

@@ -19,11 +19,12 @@ from typing import Callable, Iterable, List, Optional, Tuple, Union
 import numpy as np
 
 from .. import _device as dv
-from .. import _lib, _ops, _routes
+from .. import _lib, _ops
 from ..special.flooring import identity, max_flooring
 from ..utils.flooring import choose_flooring_fn, device_flooring, host_floor, require_device_floor
 from ..utils.select_pair import resolve_pairs, sequential_pair_selector
-from ._device_state import DeviceStateMixin, Synced
+from ._device_state import LossShares, Synced
+from ._filter_base import _IP1, _IP2, _IPA, _ISS1, _ISS2, DemixingFilterBase
 from .base import IterativeMethodBase
 
 __all__ = ["AuxIVA", "AuxLaplaceIVA", "AuxGaussIVA"]
@@ -31,20 +32,9 @@ __all__ = ["AuxIVA", "AuxLaplaceIVA", "AuxGaussIVA"]
 spatial_algorithms = ["IP", "IP1", "IP2", "ISS", "ISS1", "ISS2", "IPA"]
 EPS = 1e-10
 
-_IP1 = ("IP", "IP1")
-_ISS1 = ("ISS", "ISS1")
-_IP2 = ("IP2",)
-_ISS2 = ("ISS2",)
-_IPA = ("IPA",)
-_PROJECTION_BACK = ("projection_back",)
-_MDP = ("minimal_distortion_principle",)
 
-
-class IVABase(DeviceStateMixin, IterativeMethodBase):
+class IVABase(DemixingFilterBase):
     """ref: ssspy/bss/iva.py:48-281."""
-
-    demix_filter = Synced(dv.c128)
-    output = Synced(dv.c128)
 
     def __init__(
         self,
@@ -88,109 +78,6 @@ class IVABase(DeviceStateMixin, IterativeMethodBase):
         W = dv.to_device(demix_filter if batched else demix_filter[None], dtype=np.complex128)
         Y = dv.to_host(_ops.separate(X, W))
         return Y if batched else Y[0]
-
-    def _uses_filter(self) -> bool:
-        return not self._state_is_none("demix_filter")
-
-    def _implied_filter(self):
-        """W with output = W x while nothing else rewrote ``output`` since, else None (the ISS2 / IPA
-        iterations of AuxIVA keep it, see AuxIVA._update_once_implied)."""
-        kept = getattr(self, "_implied", None)
-        if (kept is None or kept[1] != self._state_rev("output")
-                or not _routes.get("implied_filter")):
-            return None
-        return kept[0]
-
-    def _fill_output_from_implied_filter(self) -> None:
-        _ops.separate(self._X, self._implied[0], out=self._state()["output"]["dev"])
-
-    def _leave_implied_route(self) -> None:
-        """Form Y = W x now and go on with the iterations that rewrite it (the reference's)."""
-        W = self._implied[0]
-        self._state_dev("output")  # (runs the deferred fill)
-        if getattr(self, "_logdet_cache", None) is not None:
-            self._logdet_cache = (_ops.sum_logdet(W), self._state_rev("output"))
-        self._implied = None
-        self._r2_cache = None
-
-    def _resolve_floor(self, flooring_fn):
-        if type(flooring_fn) is str and flooring_fn == "self":
-            return self._floor
-        return device_flooring(choose_flooring_fn(flooring_fn, method=self), allow_host=True)
-
-    def _host_loss(self, data, logdet_sum):
-        self._check_device_errors()
-        values = dv.to_host(data) - 2.0 * dv.to_host(logdet_sum)
-        return values.copy() if self._batched else values[0].item()
-
-    def restore_scale(self) -> None:
-        """ref: ssspy/bss/iva.py:238-257."""
-        scale_restoration = self.scale_restoration
-        assert scale_restoration, "Set self.scale_restoration=True."
-        if type(scale_restoration) is bool:
-            scale_restoration = _PROJECTION_BACK[0]
-        if scale_restoration in _PROJECTION_BACK:
-            self.apply_projection_back()
-        elif scale_restoration in _MDP:
-            self.apply_minimal_distortion_principle()
-        else:
-            raise ValueError("{} is not supported for scale restoration.".format(scale_restoration))
-
-    def apply_projection_back(self) -> None:
-        """ref: ssspy/bss/iva.py:259-267, :2194-2204; algorithm/projection_back.py:87-121."""
-        assert self.scale_restoration, "Set self.scale_restoration=True."
-        info = self._info_tensor()
-        if self._uses_filter():
-            W = self._state_dev("demix_filter")
-            _ops.projection_back_filter(W, self.reference_id, info)
-            self._state_touch("demix_filter")
-            self._state_set_dev("output", _ops.separate(self._X, W))
-        elif self._implied_filter() is not None and self.reference_id is not None:
-            # the same scales from the filters the output state implies: one pass instead of four
-            W = self._implied_filter().clone()
-            _ops.projection_back_filter(W, self.reference_id, info)
-            self._state_set_dev("output", _ops.separate(self._X, W))
-            self._implied = (W, self._state_rev("output"))
-        else:
-            Y = self._state_dev("output")
-            XY = _ops.cross_covariance(self._X, Y)
-            YY = _ops.cross_covariance(Y, Y)
-            G = _ops.projection_back_scale(XY, YY, self.reference_id, info)
-            _ops.separate(Y, G, out=Y)
-            self._state_touch("output")
-
-    def apply_minimal_distortion_principle(self) -> None:
-        """Per (bin, source) scale z = <y, x_ref> / <y, y>, output conj(z) y; with a filter state the
-        filter is re-fitted as Y X^H (X X^H)^-1 like the reference.
-        ref: ssspy/bss/iva.py:269-281, :2206-2214; algorithm/minimal_distortion_principle.py:6-43."""
-        assert self.scale_restoration, "Set self.scale_restoration=True."
-        filt = self._uses_filter()
-        if self.reference_id is None:
-            # reachable only by clearing the attribute after construction; as in the reference the
-            # estimate gains a leading channel axis (minimal_distortion_principle.py:34-35) and a
-            # filter state cannot take that shape
-            if filt:
-                raise ValueError("reference_id=None needs the output state (ISS / IPA), not filters.")
-            from ..algorithm import minimal_distortion_principle as _mdp
-
-            Y, X = dv.to_host(self._state_dev("output")), dv.to_host(self._X)
-            out = np.stack([_mdp(y, reference=x, reference_id=None) for y, x in zip(Y, X)])
-            self.output = out if self._batched else out[0]
-            return
-        if filt:
-            Y = _ops.separate(self._X, self._state_dev("demix_filter"))
-        else:
-            Y = self._state_dev("output")
-        G = _ops.mdp_scale(_ops.cross_covariance(Y, self._X), _ops.cross_covariance(Y, Y),
-                           self.reference_id)
-        _ops.separate(Y, G, out=Y)
-        if filt:
-            W = _ops.demix_from_covariance(_ops.cross_covariance(Y, self._X), self._C(),
-                                           self._info_tensor())
-            self._state_set_dev("demix_filter", W)
-            self._state_set_dev("output", Y)
-        else:
-            self._state_touch("output")
 
 
 class AuxIVABase(IVABase):
@@ -290,92 +177,63 @@ class AuxIVA(AuxIVABase):
         self._reset(**kwargs)
         if not self._iterate_with_resident_loss(int(n_iter), initial_call):
             IterativeMethodBase.__call__(self, n_iter=n_iter, initial_call=initial_call)
-        if self.scale_restoration:
-            self.restore_scale()
-        if self._uses_filter():
-            self._state_set_dev("output", _ops.separate(self._X, self._state_dev("demix_filter")))
-        return self._final_output()
+        return self._finish_call()
 
     def _iterate_with_resident_loss(self, n_iter: int, initial_call: bool) -> bool:
         """IP1 with ``record_loss=True`` (the reference's default) at the cost of ``record_loss=False``.
 
         ``compute_loss()`` needs the frame powers of the current estimate -- a pass over the mixture
         -- and so does the next ``update_once()``: here the loss of the state after iteration t is
-        taken from the frame powers iteration t + 1 forms anyway, all loss terms stay in HBM, and
-        the list is assembled from one download at the end.  Only when nothing can look at
-        ``self.loss`` in between (no callbacks, stock methods, a contrast that runs on the device
-        and keeps no variance state); otherwise (returns False) the reference's loop runs unchanged.
+        taken from the frame powers iteration t + 1 forms anyway (_resident_loss).  Only when
+        nothing can look at ``self.loss`` in between (no callbacks, stock methods, a contrast that
+        runs on the device and keeps no variance state); else the plain step of
+        _iterate_with_resident_terms, if that applies, or (returns False) the reference's loop.
         ref: ssspy/bss/base.py:68-77, ssspy/bss/iva.py:200-222, :1736-1793."""
         cls = type(self)
-        if not (self.record_loss and not self.callbacks and n_iter > 0
+        B, N = self._X.shape[0], self.n_sources
+        # (round 6) sum_i log|det W_i| of the state an update starts from is a by-product of that
+        # update: one share per 16-bin tile from the latency form of IP1 for a handful of mixtures
+        # (the one-block sum_logdet launch was 13 us of a 65 us iteration), else the finished sum;
+        # folded once at the end, only the last state needs sum_logdet
+        nld = _ops.update_by_ip1_logdet_slots(B, self.n_bins, N)
+        if not (self._unobserved_loss(n_iter)
                 and self.spatial_algorithm in _IP1 and self._contrast is not None
                 and host_floor(self._floor) is None
                 and self._variance_tensor() is None
                 and cls.update_once is AuxIVA.update_once
                 and cls.update_once_ip1 is AuxIVA.update_once_ip1
-                and cls.compute_loss is AuxIVA.compute_loss):
-            return self._iterate_with_resident_terms(n_iter, initial_call)
-        B, dev, N = self._X.shape[0], self._X.device, self.n_sources
-        data = dv.zeros((n_iter + 1, B), dv.f64, dev)
-        logdet = dv.zeros((n_iter + 1, B), dv.f64, dev)
-        W = self._state_dev("demix_filter")
-        floor = self._resolve_floor("self")
-        # (round 6) sum_i log|det W_i| of the state an update starts from is a by-product of that
-        # update: one share per 16-bin tile from the latency form of IP1 for a handful of mixtures
-        # (the one-block sum_logdet launch was 13 us of a 65 us iteration), else the finished sum;
-        # folded once at the end, only the last state needs sum_logdet
-        stride = (n_iter + 1) * B
-        nld = _ops.update_by_ip1_logdet_slots(B, self.n_bins, N)
-        ld = dv.zeros((nld, stride), dv.f64, dev) if nld > 1 else logdet
-        ld_flat = ld.reshape(-1)
-        for t in range(n_iter + 1):
-            r2 = _ops.iva_frame_power(self._X, W)
-            if t > 0 or initial_call:
-                _ops.iva_loss_data(r2, None, self.n_bins, self._contrast, out=data[t])
-            if t == n_iter:
-                break
-            weight = _ops.iva_weight(r2, self.n_bins, self._contrast, floor, variance=None)
-            U = _ops.weighted_covariance(self._X, weight, _lib.WEIGHT_FRAME, N)
-            _ops.update_by_ip1_logdet(W, U, floor, self._info_tensor(), ld_flat[t * B:], stride)
-        if nld > 1:
-            _ops.fold_scalar_slots(ld, stride, nld, logdet.reshape(-1))
-        _ops.sum_logdet(W, out=logdet[n_iter])
-        self._state_touch("demix_filter")
-        self._check_device_errors()
-        values = dv.to_host(data) - 2.0 * dv.to_host(logdet)
-        if not initial_call:
-            values = values[1:]
-        self.loss.extend(v.copy() if self._batched else v[0].item() for v in values)
-        return True
+                and cls.compute_loss is AuxIVA.compute_loss
+                and LossShares.fit(nld, n_iter + 1, B)):
+            # the same for every other spatial algorithm (round 6): one mixture of configs[2]
+            # (ISS, 8 sources) spent 0.9-1.2 ms of wall time per 0.2 ms iteration waiting for the
+            # loss; the fused ISS sweep's frame powers and tracked log-determinant serve as they come
+            return (self._unobserved_loss(n_iter) and self._contrast is not None
+                    and cls.update_once in (AuxIVA.update_once, AuxGaussIVA.update_once)
+                    and cls.compute_loss is AuxIVA.compute_loss
+                    and self._iterate_with_resident_terms(n_iter, initial_call))
 
-    def _iterate_with_resident_terms(self, n_iter: int, initial_call: bool) -> bool:
-        """The same for every other spatial algorithm (round 6): ``compute_loss()`` downloads two
-        numbers per mixture, and the wait for them drained the queue after every iteration -- one
-        mixture of configs[2] (ISS, 8 sources) spent 0.9-1.2 ms of wall time per 0.2 ms iteration.
-        Here the terms of every iteration stay in HBM (the fused ISS sweep's frame powers and
-        tracked log-determinant serve as they come) and one download assembles the list.  Only
-        with the library's own ``update_once`` / ``compute_loss`` and a contrast that runs on the
-        device; otherwise (returns False) the reference's loop runs unchanged."""
-        cls = type(self)
-        if not (self.record_loss and not self.callbacks and n_iter > 0
-                and self._contrast is not None
-                and cls.update_once in (AuxIVA.update_once, AuxGaussIVA.update_once)
-                and cls.compute_loss is AuxIVA.compute_loss):
-            return False
-        B, dev = self._X.shape[0], self._X.device
-        data = dv.zeros((n_iter + 1, B), dv.f64, dev)
-        logdet = dv.zeros((n_iter + 1, B), dv.f64, dev)
-        for t in range(n_iter + 1):
-            if t > 0 or initial_call:
-                self._loss_terms(data[t], logdet[t])
-            if t < n_iter:
-                self.update_once()
-        self._check_device_errors()
-        values = dv.to_host(data) - 2.0 * dv.to_host(logdet)
-        if not initial_call:
-            values = values[1:]
-        self.loss.extend(v.copy() if self._batched else v[0].item() for v in values)
-        return True
+        def prepare(data, logdet):
+            W = self._state_dev("demix_filter")
+            floor = self._resolve_floor("self")
+            ld = LossShares(nld, n_iter + 1, B, self._X.device, logdet)
+
+            def step(t, record):
+                r2 = _ops.iva_frame_power(self._X, W)
+                if record:
+                    _ops.iva_loss_data(r2, None, self.n_bins, self._contrast, out=data[t])
+                weight = _ops.iva_weight(r2, self.n_bins, self._contrast, floor, variance=None)
+                U = _ops.weighted_covariance(self._X, weight, _lib.WEIGHT_FRAME, N)
+                _ops.update_by_ip1_logdet(W, U, floor, self._info_tensor(), ld.at(t), ld.stride)
+
+            def end():
+                _ops.iva_loss_data(_ops.iva_frame_power(self._X, W), None, self.n_bins,
+                                   self._contrast, out=data[n_iter])
+                ld.fold()
+                _ops.sum_logdet(W, out=logdet[n_iter])
+                self._state_touch("demix_filter")
+
+            return step, end
+        return self._resident_loss(n_iter, initial_call, prepare)
 
     def __repr__(self) -> str:
         s = "AuxIVA(spatial_algorithm={}, scale_restoration={}, record_loss={}".format(
@@ -391,30 +249,14 @@ class AuxIVA(AuxIVABase):
         # (also here, not only in __call__: update_once() after a manual _bind_input() / _reset() --
         #  the benchmarks do that, and the reference allows it -- must find the contrast code)
         self._contrast = _device_contrast(self.contrast_fn, self.d_contrast_fn)
-        self._logdet_cache = None
-        self._implied = None
-        B, N, F, T = self._X.shape
-        self._amp_reset()
-        if self.spatial_algorithm in _ISS2 + _IPA and N <= 4:
-            # the filters the output state implies (output = W x): the ISS2 / IPA iterations read the
-            # mixture through them (_update_once_implied).  Up to 4 sources (the tuned covariance
-            # pass).  W U W^H rounds like eps |W|^2 |U|, the direct sum over Y like eps |y|^2: next
-            # to singular covariances lose digits -- every launch measures by how much and the
-            # route is left past the bound (_amp_exceeded, see ilrma.py)
-            self._implied = (self._state_dev("demix_filter").clone(), self._state_rev("output"))
-        if self.spatial_algorithm in ["ISS", "ISS1", "ISS2", "IPA"] and not self.record_loss:
-            self.demix_filter = None  # (nothing reads the log-determinant: no tracker)
-        elif self.spatial_algorithm in ["ISS", "ISS1", "ISS2", "IPA"]:
-            # sum_i log|det W_i| of the filters the ISS state stops carrying, as (tensor, revision of
-            # `output` it describes): the fused sweep kernel moves it along (each sweep multiplies
-            # det W_i by d_in^(-1/2)), so compute_loss() need not rebuild W from Y X^H
-            self._logdet_cache = (_ops.sum_logdet(self._state_dev("demix_filter")),
-                                  self._state_rev("output"))
-            self.demix_filter = None
+        self._reset_output_state()
         # frame powers of the output (ISS state) as (tensor, revision of `output` they describe): any
         # later write to the output -- a kernel, scale restoration, an assignment by a callback --
         # changes the revision and retires the cache
         self._r2_cache = None
+
+    def _implied_route_wanted(self) -> bool:
+        return self.spatial_algorithm in _ISS2 + _IPA
 
     def _variance_tensor(self):
         return None
@@ -501,13 +343,14 @@ class AuxIVA(AuxIVABase):
 
     def update_once_ipa(self, flooring_fn="self") -> None:
         """Iterative projection with adjustment.  ref: ssspy/bss/iva.py:2068-2175."""
-        require_device_floor(self._resolve_floor(flooring_fn), "IPA")
+        floor = self._resolve_floor(flooring_fn)
+        require_device_floor(floor, "IPA")
         if self._update_once_implied(flooring_fn):
             return
         Y = self._state_dev("output")
         weight = self._weights(flooring_fn)
         r2 = _ops.update_by_ipa(Y, weight, _lib.WEIGHT_FRAME, self.lqpqm_normalization,
-                                self.newton_iter, self._resolve_floor(flooring_fn),
+                                self.newton_iter, floor, self._newton_words(Y.device),
                                 self._info_tensor(), not_converged=self._newton_counter(),
                                 frame_power=True)
         self._state_touch("output")
@@ -565,30 +408,11 @@ class AuxIVA(AuxIVABase):
             return False
         if self._amp_exceeded():
             self._leave_implied_route()
+            self._r2_cache = None
             return False
-        B, N, F, T = self._X.shape
-        dev = self._X.device
         weight = self._weights(flooring_fn)  # (frame powers through _frame_power(): |W x|^2)
-        U = _ops.weighted_covariance(self._X, weight, _lib.WEIGHT_FRAME, N)
-        Vc = getattr(self, "_Vc_implied", None)
-        if Vc is None or tuple(Vc.shape) != tuple(U.shape) or Vc.data_ptr() == U.data_ptr():
-            Vc = self._Vc_implied = dv.empty(tuple(U.shape), dv.c128, dev)
-        tracked = self._amp_tracked(self._C())
-        _ops.covariance_congruence(U, W, Vc, tracked=tracked)
-        self._amp_launched(tracked)
-        if self.spatial_algorithm in _ISS2:
-            G = _ops.iss2_transform(Vc, resolve_pairs(getattr(self, "pair_selector", None), N),
-                                    floor, self._info_tensor())
-        else:
-            G = _ops.ipa_sweep(Vc, self.lqpqm_normalization, self.newton_iter, floor,
-                               self._info_tensor(), newton_ws=self._newton_words(dev),
-                               not_converged=self._newton_counter())
-        spare = getattr(self, "_implied_spare", None)
-        if spare is None or spare.shape != W.shape or spare.data_ptr() == W.data_ptr():
-            spare = dv.empty(tuple(W.shape), dv.c128, dev)
-        _ops.compose_filters(G, W, spare)
-        self._state_defer("output", self._fill_output_from_implied_filter)
-        self._implied, self._implied_spare = (spare, self._state_rev("output")), W
+        self._implied_step(_ops.weighted_covariance(self._X, weight, _lib.WEIGHT_FRAME,
+                                                    self._X.shape[1]), floor)
         self._r2_cache = None
         return True
 
@@ -610,7 +434,7 @@ class AuxIVA(AuxIVABase):
         if host_floor(floor) is not None:
             _ops.update_by_iss1_host_floor(Y, weight, _lib.WEIGHT_FRAME, floor.host)
             self._state_touch("output")
-            self._logdet_cache = None
+            self._restamp_logdet(None)
         elif self.n_frames <= _ops.iss1_fused_max_frames(N):
             # one read + one write of Y; the kernel also leaves the next iteration's frame powers
             r2_next = dv.empty(tuple(weight.shape), dv.f64, Y.device)
@@ -618,7 +442,7 @@ class AuxIVA(AuxIVABase):
             _ops.iss1_fused(Y, weight, _lib.WEIGHT_FRAME, floor, r2_next, logdet=tracked)
             self._state_touch("output")
             self._r2_cache = (r2_next, self._state_rev("output"))
-            self._logdet_cache = None if tracked is None else (tracked, self._state_rev("output"))
+            self._restamp_logdet(tracked)
         else:
             Vc = _ops.weighted_covariance(Y, weight, _lib.WEIGHT_FRAME, N)
             G = _ops.iss1_transform(Vc, floor)
@@ -632,13 +456,6 @@ class AuxIVA(AuxIVABase):
             _ops.separate(Y, G, out=Y)
         self._state_touch("output")
         self._r2_cache = None if r2 is None else (r2, self._state_rev("output"))
-
-    def _tracked_logdet(self):
-        """The tracked sum_i log|det W_i| if it describes the current output, else None."""
-        cache = getattr(self, "_logdet_cache", None)
-        if cache is not None and cache[1] == self._state_rev("output"):
-            return cache[0]
-        return None
 
     def _logdet_sum(self):
         """sum_i log|det W_i| (B,) on the device, and the filters if they had to be formed."""

@@ -25,7 +25,7 @@ from .. import _lib, _ops
 from ..special.flooring import identity, max_flooring
 from ..utils.flooring import choose_flooring_fn, device_flooring, host_floor, require_device_floor
 from ..utils.select_pair import resolve_pairs, sequential_pair_selector
-from ._device_state import DeviceStateMixin, Synced
+from ._device_state import DeviceStateMixin, LossShares, Synced
 from .base import IterativeMethodBase
 
 __all__ = ["FastGaussMNMF", "GaussMNMF"]
@@ -383,10 +383,7 @@ class FastGaussMNMF(FastMNMFBase):
 
     def compute_loss(self) -> float:
         """ref: ssspy/bss/mnmf.py:1219-1261."""
-        data, logdet = self._loss_terms()
-        self._check_device_errors()
-        values = dv.to_host(data) - 2.0 * dv.to_host(logdet)
-        return values.copy() if self._batched else values[0].item()
+        return self._host_loss(*self._loss_terms())
 
     def _stock_ip1_iteration(self) -> bool:
         """update_once() is the one fused C-ABI call (stock step methods, IP1, power normalisation)."""
@@ -407,69 +404,53 @@ class FastGaussMNMF(FastMNMFBase):
         stock ``update_once`` / ``compute_loss``); otherwise (returns False) the reference's loop
         runs unchanged.  ref: ssspy/bss/base.py:68-77, ssspy/bss/mnmf.py:1219-1261."""
         cls = type(self)
-        if not (self.record_loss and not self.callbacks and n_iter > 0
-                and self._stock_ip1_iteration()
+        if not (self._unobserved_loss(n_iter) and self._stock_ip1_iteration()
                 and cls.update_once is FastGaussMNMF.update_once
                 and cls.compute_loss is FastGaussMNMF.compute_loss):
             return False
-        B, dev = self._X.shape[0], self._X.device
-        data = dv.zeros((n_iter + 1, B), dv.f64, dev)
-        logdet = dv.zeros((n_iter + 1, B), dv.f64, dev)
-        if host_floor(self._floor) is not None:
-            if initial_call:
-                self._loss_terms(data[0], logdet[0])
-            for t in range(n_iter):
-                self.update_once()
-                self._loss_terms(data[t + 1], logdet[t + 1])
-        else:
-            # Round 6: sum_i log|det Q_i| of the state iteration t + 1 starts from is a by-product of
-            # that iteration (the latency form of IP1 reads the diagonalisers anyway and leaves one
-            # share per 16-bin tile; elsewhere the call stores the finished sum) -- folded once at
-            # the end; only the last state needs sum_logdet.  The data term stays a pass per state.
-            stride = (n_iter + 1) * B
-            nld = _ops.fastmnmf_deferred_logdet_slots(B, self.n_sources, self.n_channels,
-                                                      self.n_bins, self.n_frames, self.n_basis)
-            ld = dv.zeros((nld, stride), dv.f64, dev) if nld > 1 else logdet
-            ld_flat = ld.reshape(-1)
+        B, dims = self._X.shape[0], (self.n_sources, self.n_channels, self.n_bins, self.n_frames,
+                                     self.n_basis)
+        # Round 6: sum_i log|det Q_i| of the state iteration t + 1 starts from is a by-product of
+        # that iteration (the latency form of IP1 reads the diagonalisers anyway and leaves one
+        # share per 16-bin tile; elsewhere the call stores the finished sum) -- folded once at the
+        # end; only the last state needs sum_logdet.  The data term stays a pass per state.
+        nld = _ops.fastmnmf_deferred_logdet_slots(B, *dims)
+        if host_floor(self._floor) is not None or not LossShares.fit(nld, n_iter + 1, B):
+            return self._iterate_with_resident_terms(n_iter, initial_call)
+
+        def prepare(data, logdet):
+            dev = self._X.device
+            ld = LossShares(nld, n_iter + 1, B, dev, logdet)
             steps = _lib.MNMF_ALL if self.normalization else _lib.MNMF_ALL & ~_lib.MNMF_NORMALIZE
             # the data term from the |Q x|^2 hand-over leaves its per-wave shares raw in one array
             # for the whole run (no memsets, no fold launch per loss)
-            nds = _ops.fastmnmf_loss_handover_slots(B, self.n_sources, self.n_channels, self.n_bins,
-                                                    self.n_frames, self.n_basis)
-            ds = dv.zeros((nds, stride), dv.f64, dev) if nds and nds * stride * 8 <= (1 << 28) else None
-            ds_flat = ds.reshape(-1) if ds is not None else None
+            nds = _ops.fastmnmf_loss_handover_slots(B, *dims)
+            ds = LossShares(nds, n_iter + 1, B, dev) if nds and LossShares.fit(nds, n_iter + 1, B) \
+                else None
 
             def data_term(t):
                 if ds is not None and self._handover_valid():
                     _ops.fastmnmf_loss_data_handover_slots(
                         self._state_dev("spatial"), self._state_dev("basis"),
                         self._state_dev("activation"), self._handover, self.n_channels,
-                        self.n_frames, ds_flat[t * B:], stride)
+                        self.n_frames, ds.at(t), ds.stride)
                 else:
                     self._loss_terms(data[t], None)
 
-            if initial_call:
-                data_term(0)
-            for t in range(n_iter):
-                self._update(steps, "self", logdet=ld_flat[t * B:], logdet_stride=stride)
-                data_term(t + 1)
-            if nld > 1:
-                _ops.fold_scalar_slots(ld, stride, nld, logdet.reshape(-1))
-            _ops.sum_logdet(self._state_dev("diagonalizer"), out=logdet[n_iter])
-            if ds is not None:  # (every state has its data term in `data` or in the shares)
-                folded = dv.zeros((n_iter + 1, B), dv.f64, dev)
-                _ops.fold_scalar_slots(ds, stride, nds, folded.reshape(-1))
-                data = (data, folded)
-        self._check_device_errors()
-        if isinstance(data, tuple):
-            data = dv.to_host(data[0]) + dv.to_host(data[1])
-        else:
-            data = dv.to_host(data)
-        values = data - 2.0 * dv.to_host(logdet)
-        if not initial_call:
-            values = values[1:]
-        self.loss.extend(v.copy() if self._batched else v[0].item() for v in values)
-        return True
+            def step(t, record):
+                if record:
+                    data_term(t)
+                self._update(steps, "self", logdet=ld.at(t), logdet_stride=ld.stride)
+
+            def end():
+                data_term(n_iter)
+                ld.fold()
+                _ops.sum_logdet(self._state_dev("diagonalizer"), out=logdet[n_iter])
+                # (every state has its data term in `data` or in the shares)
+                return None if ds is None else ds.fold()
+
+            return step, end
+        return self._resident_loss(n_iter, initial_call, prepare)
 
     def compute_logdet(self, diagonalizer: np.ndarray) -> np.ndarray:
         """log|det Q_i| per bin (ref: ssspy/bss/mnmf.py:1263-1276); host-side convenience."""

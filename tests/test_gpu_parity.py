@@ -435,6 +435,24 @@ def test_ilrma_folded_power_normalization_equals_three_pass_form(algo, N, B, mon
             assert err(Y if B == 1 else Y[0], Yr) < 1e-7
 
 
+def test_single_source_ilrma_stays_off_the_implied_filter_route():
+    """One source, ISS1, B * F >= 4096 (round 6 advisor finding): the implied-filter route asks for
+    the tracked congruence, which exists for 2..4 sources only, so it is not taken at N = 1.  The
+    ILRMA kernels themselves take 2..8 sources: the call stops at their bound."""
+    from ssspy_amd.bss.ilrma import GaussILRMA
+    from ssspy_amd.utils.dataset import nmf_mixture
+
+    F, T, K = 4096, 16, 2
+    for N in (1, 2):
+        m = GaussILRMA(n_basis=K, spatial_algorithm="ISS1", record_loss=False)
+        m._bind_input(nmf_mixture(41, N, F, T))
+        m._reset(flooring_fn=m.flooring_fn)
+        assert (m._implied_filter() is not None) == (N == 2)
+    with pytest.raises(NotImplementedError, match="n_sources"):
+        GaussILRMA(n_basis=K, spatial_algorithm="ISS1", record_loss=False)(
+            nmf_mixture(41, 1, F, T), n_iter=2)
+
+
 @pytest.mark.parametrize("family,algo,N,F,T,seed", [
     ("ilrma", "ISS2", 3, 33, 8, 0), ("ilrma", "ISS2", 3, 33, 8, 3), ("ilrma", "ISS2", 4, 31, 11, 6),
     ("ilrma", "IPA", 4, 31, 11, 4), ("iva", "ISS2", 4, 31, 64, "ill"), ("iva", "IPA", 3, 24, 48, "ill")])
