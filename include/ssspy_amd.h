@@ -70,8 +70,10 @@ enum { SSSPY_SOURCE_ME = 0x100 };
  * iteration on the Gauss model's tuned passes run with the source count at run time (wide_n.hip:
  * correct, not tuned; the reference has no limit: ssspy/bss/ilrma.py:180, iva.py:152), IPA included
  * (ssspy_ipa_sweep, ipa_rt.hip, round 6), and so do the Hermitian operators / ssspy_solve (to
- * 16 x 16) and the standalone ssspy_lqpqm2 (to dimension 15; hermitian_rt.hip).  The MNMF entry
- * points and the ssspy_ilrma_partition_* entry points (partitioning=True) stay at SSSPY_MAX_SOURCES
+ * 16 x 16) and the standalone ssspy_lqpqm2 (to dimension 15; hermitian_rt.hip).  The
+ * ssspy_fastmnmf_* entry points take n_channels in [2, 16] and n_sources in [1, 16] (9..16 of either
+ * on the run-time forms of fmnmf_rt.hip; SSSPY_ERR_UNSUPPORTED above 16).  The GaussMNMF entry points
+ * and the ssspy_ilrma_partition_* entry points (partitioning=True) stay at SSSPY_MAX_SOURCES
  * (SSSPY_ERR_UNSUPPORTED above). */
 #define SSSPY_RT_MAX_SOURCES 16
 /* n_basis: the kernels walk any number of bases (dense products above 32; checked against the
@@ -637,7 +639,9 @@ int ssspy_fastmnmf_loss_data_handover_slots(const double *D, const double *basis
 /* U[b,i,m] = (1/T) sum_j x x^H / R~_ijm  -> (B,F,M,M,M): the covariances the diagonaliser update
  * (IP1 inside ssspy_fastmnmf_update, or ssspy_update_by_ip2 for diagonalizer_algorithm="IP2") needs.
  * workspace: NULL, or ssspy_fastmnmf_workspace_bytes() of scratch -- with it the tuned pass of the
- * fused update runs (its split work items park partial sums there).
+ * fused update runs (its split work items park partial sums there).  N, M <= 4, or 9..16 channels or
+ * sources (one fused pass on the matrix cores that forms the weights itself; the workspace is not
+ * used); 5..8 return SSSPY_ERR_UNSUPPORTED (use ssspy_fastmnmf_weights + ssspy_weighted_covariance).
  * replaces: ssspy/bss/mnmf.py:1504-1512, :1621-1629. */
 int ssspy_fastmnmf_diagonalizer_covariance(const void *X, const double *D, const double *basis,
                                            const double *activation, void *U, int B, int N, int M,
@@ -646,7 +650,7 @@ int ssspy_fastmnmf_diagonalizer_covariance(const void *X, const double *D, const
 
 /* weights[b,m,i,j] = 1 / R~_ijm, R~ = sum_n lambda_nij d_inm (B,M,F,T): the per-channel weights of the
  * diagonaliser covariance, U = ssspy_weighted_covariance(X, weights, SSSPY_WEIGHT_BIN_FRAME, S = M).
- * Any n_sources <= 8, n_channels in [2, 8].  replaces: ssspy/bss/mnmf.py:1489-1512 (the weight part). */
+ * Any n_sources <= 16, n_channels in [2, 16].  replaces: ssspy/bss/mnmf.py:1489-1512 (the weight part). */
 int ssspy_fastmnmf_weights(const void *X, const void *Q, const double *D, const double *basis,
                            const double *activation, double *weights, int B, int N, int M, int F,
                            int T, int K, void *stream);

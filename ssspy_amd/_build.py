@@ -58,6 +58,7 @@ def _units():
         ("hermitian_ops.hip", "hermitian_ops.o", []),
         ("hermitian_rows.hip", "hermitian_rows.o", []),
         ("fmnmf_generic.hip", "fmnmf_generic.o", []),
+        ("fmnmf_rt.hip", "fmnmf_rt.o", []),
         ("wide_cov.hip", "wide_cov.o", []),
         ("wide_n.hip", "wide_n.o", []),
         ("wide_basis.hip", "wide_basis.o", []),

@@ -234,8 +234,12 @@ class FastMNMFBase(MNMFBase):
             self._state_touch("spatial")
 
     def _diagonalizer_covariance(self):
-        """U_m = mean_j x x^H / R~_m (B, F, M, M, M): the weights of the diagonaliser updates."""
-        if self.n_sources <= 4 and self.n_channels <= 4 and self.n_sources >= 2:
+        """U_m = mean_j x x^H / R~_m (B, F, M, M, M): the weights of the diagonaliser updates.  The
+        fused pass serves N, M <= 4 (the tuned one) and 9..16 sources or channels (the run-time one,
+        which forms the weights itself); 5..8 go through the (B, M, F, T) weights."""
+        N, M = self.n_sources, self.n_channels
+        wide = max(N, M) > _lib.MAX_SOURCES
+        if (N <= 4 and M <= 4 and N >= 2) or wide:
             return _ops.fastmnmf_diagonalizer_covariance(
                 self._X, self._state_dev("spatial"), self._state_dev("basis"),
                 self._state_dev("activation"), ws=self._ws, ws_bytes=self._ws_bytes)

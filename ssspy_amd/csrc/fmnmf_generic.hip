@@ -1,4 +1,5 @@
-// FastGaussMNMF, general shapes: any n_channels M in [2, 8] and n_sources N in [1, 8].
+// FastGaussMNMF, general shapes: any n_channels M in [2, 8] and n_sources N in [1, 8]; beyond
+// (M or N in 9..16) the same orchestration hands the M- and N-shaped passes to fmnmf_rt.hip.
 //
 // The MFMA-tile kernels of mnmf_kernels.hip keep the diagonaliser rows, the spatial rows and the
 // GEMM1 output of every source in registers and are compiled for N, M <= 4.  Beyond that the unit of
@@ -24,6 +25,35 @@ namespace ssspy {
 int ip1_with_power(void *W, const void *U, const void *C, double *qbuf, int B, int F, int N,
                    int floor_kind, double floor_eps, int *info, hipStream_t st);
 int row_power(const void *W, const void *C, double *qbuf, int B, int F, int N, hipStream_t st);
+
+// the run-time-M / N forms (fmnmf_rt.hip) for M or N in 9..16
+bool fmnmf_rt_shape(int N, int M);
+int fmnmf_rt_walk(int mode, const void *X, const void *Q, const void *Qinv, const double *D,
+                  const double *basis, const double *act, double *out0, double *out1, void *Y,
+                  int B, int N, int M, int F, int T, int K, int ref, int floor_kind, double eps,
+                  int *redo, hipStream_t st);
+int fmnmf_rt_loss_slots(int B, int F, int T);
+int fmnmf_rt_diagonalizer_covariance(const void *X, const double *D, const double *basis,
+                                     const double *act, void *U, int B, int N, int M, int F, int T,
+                                     int K, hipStream_t st);
+int fmnmf_rt_norm_scale(void *Q, double *D, const double *qbuf, int B, int N, int M, int F,
+                        int floor_kind, double eps, hipStream_t st);
+int fmnmf_rt_separate(const void *X, const void *Q, void *Qinv, const double *D,
+                      const double *basis, const double *act, void *Y, int B, int N, int M, int F,
+                      int T, int K, int ref, int floor_kind, double eps, int *info, int *redo,
+                      hipStream_t st);
+int fmnmf_rt_separate_eig(const void *X, const void *Q, void *Qinv, const double *D,
+                          const double *basis, const double *act, void *Y, int B, int N, int M,
+                          int F, int T, int K, int ref, int stage, double *lam, void *P, int *info,
+                          hipStream_t st);
+
+// n_sources in [1, 16], n_channels in [2, 16]
+static inline int fmnmf_shape_check(int N, int M) {
+  if (N < 1 || N > SSSPY_RT_MAX_SOURCES || M < 2 || M > SSSPY_RT_MAX_SOURCES)
+    return fail(SSSPY_ERR_UNSUPPORTED,
+                "FastMNMF: n_sources must be in [1, 16] and n_channels in [2, 16]");
+  return SSSPY_OK;
+}
 
 namespace fmg {
 
@@ -745,6 +775,10 @@ static int launch_walk(const void *X, const void *Q, const void *Qinv, const dou
                        const double *basis, const double *act, double *out0, double *out1, void *Y,
                        int B, int N, int M, int F, int T, int K, int ref, int floor_kind, double eps,
                        int *redo, hipStream_t st) {
+  if (fmnmf_shape_check(N, M)) return SSSPY_ERR_UNSUPPORTED;
+  if (fmnmf_rt_shape(N, M))
+    return fmnmf_rt_walk(MODE, X, Q, Qinv, D, basis, act, out0, out1, Y, B, N, M, F, T, K, ref,
+                         floor_kind, eps, redo, st);
   // point_terms keeps lam[NMAX]: more sources would silently drop out of R~
   if (N < 1 || N > NMAX) return fail(SSSPY_ERR_UNSUPPORTED, "FastMNMF: n_sources must be in [1, 8]");
   const WalkPlan p = walk_plan(B, F, T);
@@ -761,11 +795,12 @@ static int launch_walk(const void *X, const void *Q, const void *Qinv, const dou
 // ---- entry points used by mnmf_api.hip for shapes outside the MFMA-tile kernels
 size_t fmnmf_generic_workspace_doubles(int B, int N, int M, int F, int T) {
   // A, Bt (B,N,F,T) each -- or, for the spatial update, (num, den) of every (bin, n, m) per frame
-  // tile; the (B,M,F,T) weights behind them
+  // tile; the (B,M,F,T) weights behind them (none for the run-time forms: their covariance pass
+  // forms the weights itself)
   const size_t pts = (size_t)B * F * T;
   const size_t traces = pts * (2 * (size_t)N);
   const size_t spatial = (size_t)((T + 63) / 64) * B * F * N * M * 2;
-  return (traces > spatial ? traces : spatial) + pts * (size_t)M;
+  return (traces > spatial ? traces : spatial) + (fmnmf_rt_shape(N, M) ? 0 : pts * (size_t)M);
 }
 
 int fmnmf_generic_update(const void *X, const void *C, void *Q, double *D, double *basis,
@@ -773,8 +808,8 @@ int fmnmf_generic_update(const void *X, const void *C, void *Q, double *D, doubl
                          int floor_kind, double floor_eps, double *gws, void *U, double *qbuf,
                          int *info, hipStream_t st) {
   using namespace fmg;
-  if (N < 1 || N > NMAX) return fail(SSSPY_ERR_UNSUPPORTED, "FastMNMF: n_sources must be in [1, 8]");
-  if (M < 2 || M > 8) return fail(SSSPY_ERR_UNSUPPORTED, "FastMNMF: n_channels must be in [2, 8]");
+  if (fmnmf_shape_check(N, M)) return SSSPY_ERR_UNSUPPORTED;
+  const bool wide = fmnmf_rt_shape(N, M);
   const size_t pts = (size_t)B * F * T;
   const size_t traces = pts * (2 * (size_t)N);
   const size_t spatial = (size_t)((T + 63) / 64) * B * F * N * M * 2;
@@ -816,10 +851,14 @@ int fmnmf_generic_update(const void *X, const void *C, void *Q, double *D, doubl
   }
   bool have_q = false;
   if (steps & SSSPY_MNMF_DIAGONALIZER) {
-    rc = launch_walk<MODE_WEIGHTS>(X, Q, nullptr, D, basis, activation, Wt, nullptr, nullptr, B, N,
-                                   M, F, T, K, 0, 0, 0.0, nullptr, st);
-    if (rc) return rc;
-    rc = ssspy_weighted_covariance(X, Wt, SSSPY_WEIGHT_BIN_FRAME, U, B, M, M, F, T, (void *)st);
+    if (wide) {
+      rc = fmnmf_rt_diagonalizer_covariance(X, D, basis, activation, U, B, N, M, F, T, K, st);
+    } else {
+      rc = launch_walk<MODE_WEIGHTS>(X, Q, nullptr, D, basis, activation, Wt, nullptr, nullptr, B,
+                                     N, M, F, T, K, 0, 0, 0.0, nullptr, st);
+      if (rc) return rc;
+      rc = ssspy_weighted_covariance(X, Wt, SSSPY_WEIGHT_BIN_FRAME, U, B, M, M, F, T, (void *)st);
+    }
     if (rc) return rc;
     rc = ip1_with_power(Q, U, C, C ? qbuf : nullptr, B, F, M, floor_kind, floor_eps, info, st);
     if (rc) return rc;
@@ -840,6 +879,8 @@ int fmnmf_generic_update(const void *X, const void *C, void *Q, double *D, doubl
       rc = row_power(Q, C, qbuf, B, F, M, st);
       if (rc) return rc;
     }
+    if (wide)
+      return fmnmf_rt_norm_scale(Q, D, qbuf, B, N, M, F, floor_kind, floor_eps, st);
     hipLaunchKernelGGL(k_norm_scale, dim3((F + 63) / 64, B), dim3(256), 0, st, (c128 *)Q, D,
                        (const double *)qbuf, N, M, F, floor_kind, floor_eps);
     rc = check_launch("fmnmf_generic norm_scale");
@@ -854,12 +895,13 @@ int fmnmf_generic_weights(const void *X, const void *Q, const double *D, const d
                                              M, F, T, K, 0, 0, 0.0, nullptr, st);
 }
 
-static inline int fmg_loss_slots(int B, int F, int T) {
+static inline int fmg_loss_slots(int B, int N, int M, int F, int T) {
+  if (fmnmf_rt_shape(N, M)) return fmnmf_rt_loss_slots(B, F, T);
   const fmg::WalkPlan p = fmg::walk_plan(B, F, T);
   return p.gx * p.gy * fmg::WB;
 }
-size_t fmnmf_generic_loss_ws_bytes(int B, int F, int T) {
-  return scalar_slots_bytes(B, fmg_loss_slots(B, F, T));
+size_t fmnmf_generic_loss_ws_bytes(int B, int N, int M, int F, int T) {
+  return scalar_slots_bytes(B, fmg_loss_slots(B, N, M, F, T));
 }
 // out[b] = the data term; loss_ws: fmnmf_generic_loss_ws_bytes() (every wave writes its slot)
 int fmnmf_generic_loss(const void *X, const void *Q, const double *D, const double *basis,
@@ -868,7 +910,7 @@ int fmnmf_generic_loss(const void *X, const void *Q, const double *D, const doub
   const int rc = fmg::launch_walk<fmg::MODE_LOSS>(X, Q, nullptr, D, basis, act, (double *)loss_ws,
                                                   nullptr, nullptr, B, N, M, F, T, K, 0, 0, 0.0,
                                                   nullptr, st);
-  return rc ? rc : scalar_slots_fold(loss_ws, B, fmg_loss_slots(B, F, T), out, 0, st);
+  return rc ? rc : scalar_slots_fold(loss_ws, B, fmg_loss_slots(B, N, M, F, T), out, 0, st);
 }
 
 int fmnmf_generic_separate(const void *X, const void *Q, void *Qinv, const double *D,
@@ -877,6 +919,10 @@ int fmnmf_generic_separate(const void *X, const void *Q, void *Qinv, const doubl
                            int *redo, hipStream_t st) {
   // redo: B F ints of scratch (bins the closed-form launch hands to the general one)
   using namespace fmg;
+  if (fmnmf_shape_check(N, M)) return SSSPY_ERR_UNSUPPORTED;
+  if (fmnmf_rt_shape(N, M))
+    return fmnmf_rt_separate(X, Q, Qinv, D, basis, act, Y, B, N, M, F, T, K, ref, floor_kind, eps,
+                             info, redo, st);
   if (N < 1 || N > NMAX) return fail(SSSPY_ERR_UNSUPPORTED, "FastMNMF: n_sources must be in [1, 8]");
   const long long nbins = (long long)B * F;
   hipError_t e = hipMemsetAsync(redo, 0, (size_t)nbins * sizeof(int), st);
@@ -896,12 +942,16 @@ int fmnmf_generic_separate(const void *X, const void *Q, void *Qinv, const doubl
 
 // The Wiener filter split at the eigenvalue floor of to_psd (an arbitrary flooring callable):
 // stage 1 leaves ascending eigenvalues lam (B,F,T,M) and eigenvectors P (B,F,T,M,M); the host floors
-// lam; stage 2 finishes.  Any N, M <= 8.
+// lam; stage 2 finishes.  Any N, M <= 16.
 int fmnmf_generic_separate_eig(const void *X, const void *Q, void *Qinv, const double *D,
                                const double *basis, const double *act, void *Y, int B, int N,
                                int M, int F, int T, int K, int ref, int stage, double *lam,
                                void *P, int *info, hipStream_t st) {
   using namespace fmg;
+  if (fmnmf_shape_check(N, M)) return SSSPY_ERR_UNSUPPORTED;
+  if (fmnmf_rt_shape(N, M))
+    return fmnmf_rt_separate_eig(X, Q, Qinv, D, basis, act, Y, B, N, M, F, T, K, ref, stage, lam, P,
+                                 info, st);
   if (N < 1 || N > NMAX) return fail(SSSPY_ERR_UNSUPPORTED, "FastMNMF: n_sources must be in [1, 8]");
   const long long nbins = (long long)B * F;
   FMG_DISPATCH_M(M, {

@@ -62,7 +62,7 @@ int fmnmf_generic_update(const void *X, const void *C, void *Q, double *D, doubl
 int fmnmf_generic_weights(const void *X, const void *Q, const double *D, const double *basis,
                           const double *act, double *Wt, int B, int N, int M, int F, int T, int K,
                           hipStream_t st);
-size_t fmnmf_generic_loss_ws_bytes(int B, int F, int T);
+size_t fmnmf_generic_loss_ws_bytes(int B, int N, int M, int F, int T);
 int fmnmf_generic_loss(const void *X, const void *Q, const double *D, const double *basis,
                        const double *act, double *out, void *loss_ws, int B, int N, int M, int F,
                        int T, int K, hipStream_t st);
@@ -74,6 +74,11 @@ int fmnmf_generic_separate_eig(const void *X, const void *Q, void *Qinv, const d
                                const double *basis, const double *act, void *Y, int B, int N,
                                int M, int F, int T, int K, int ref, int stage, double *lam,
                                void *P, int *info, hipStream_t st);
+// M or N in 9..16: the run-time forms of fmnmf_rt.hip
+bool fmnmf_rt_shape(int N, int M);
+int fmnmf_rt_diagonalizer_covariance(const void *X, const double *D, const double *basis,
+                                     const double *act, void *U, int B, int N, int M, int F, int T,
+                                     int K, hipStream_t st);
 
 // the MFMA-tile kernels (mnmf_kernels.hip) are compiled for 2..4 sources and channels
 static inline bool mnmf_tiled(int N, int M) { return N >= 2 && N <= 4 && M >= 2 && M <= 4; }
@@ -116,7 +121,9 @@ static inline MnmfWs mnmf_ws(int B, int N, int M, int F, int T, int K) {
   w.qinv = off;
   off += al((size_t)B * F * M * M * 2 * sizeof(double));
   w.tail = off;
-  off += al(mnmf_tail_bytes(N, M));
+  // (only shapes up to 8 sources and channels: the run-time forms of 9..16 park no partial sums here,
+  //  and the formula gives 2 GB at 16 channels)
+  off += (N <= SSSPY_MAX_SOURCES && M <= SSSPY_MAX_SOURCES) ? al(mnmf_tail_bytes(N, M)) : 0;
   w.generic = off;
   if (!mnmf_tiled(N, M)) off += al(fmnmf_generic_workspace_doubles(B, N, M, F, T) * sizeof(double));
   w.total = off;
@@ -366,6 +373,14 @@ int ssspy_fastmnmf_diagonalizer_covariance(const void *X, const double *D, const
                                            size_t workspace_bytes, void *stream) {
   SSSPY_REQUIRE(X && D && basis && activation && U && B > 0, "fastmnmf_diagonalizer_covariance: bad argument");
   SSSPY_REQUIRE(K >= 1 && K <= SSSPY_MAX_BASIS, "fastmnmf_diagonalizer_covariance: bad n_basis");
+  SSSPY_REQUIRE(F > 0 && T > 0, "fastmnmf_diagonalizer_covariance: bad argument");
+  if (N > SSSPY_RT_MAX_SOURCES || M > SSSPY_RT_MAX_SOURCES)
+    return fail(SSSPY_ERR_UNSUPPORTED,
+                "fastmnmf_diagonalizer_covariance: n_sources and n_channels must be at most 16");
+  // 9..16 channels or sources: the fused pass of fmnmf_rt.hip (weights formed inside; no workspace)
+  if (fmnmf_rt_shape(N, M))
+    return fmnmf_rt_diagonalizer_covariance(X, D, basis, activation, U, B, N, M, F, T, K,
+                                            as_stream(stream));
   if (!mnmf_tiled(N, M))
     return fail(SSSPY_ERR_UNSUPPORTED,
                 "fastmnmf_diagonalizer_covariance: beyond 4 sources / channels use "
@@ -394,7 +409,7 @@ int ssspy_fastmnmf_weights(const void *X, const void *Q, const double *D, const 
 
 // scratch of the loss entry points (per-block / per-wave shares, added up in a fixed order)
 static size_t fastmnmf_loss_ws(int B, int N, int M, int F, int T) {
-  if (!mnmf_tiled(N, M)) return fmnmf_generic_loss_ws_bytes(B, F, T);
+  if (!mnmf_tiled(N, M)) return fmnmf_generic_loss_ws_bytes(B, N, M, F, T);
   switch (N) {
     case 2: return mnmf_loss_ws_bytes_n2(B, F);
     case 3: return mnmf_loss_ws_bytes_n3(B, F);
@@ -412,8 +427,9 @@ int ssspy_fastmnmf_loss_data(const void *X, const void *Q, const double *D, cons
                              int T, int K, void *workspace, size_t workspace_bytes, void *stream) {
   SSSPY_REQUIRE(X && Q && D && basis && activation && out && B > 0, "fastmnmf_loss_data: bad argument");
   SSSPY_REQUIRE(K >= 1 && K <= SSSPY_MAX_BASIS, "fastmnmf_loss_data: bad n_basis");
-  SSSPY_REQUIRE(N >= 1 && N <= SSSPY_MAX_SOURCES && M >= 2 && M <= 8,
-                "fastmnmf_loss_data: n_sources in [1, 8], n_channels in [2, 8]");
+  if (N < 1 || N > SSSPY_RT_MAX_SOURCES || M < 2 || M > SSSPY_RT_MAX_SOURCES)
+    return fail(SSSPY_ERR_UNSUPPORTED,
+                "fastmnmf_loss_data: n_sources must be in [1, 16] and n_channels in [2, 16]");
   SSSPY_REQUIRE(workspace && workspace_bytes >= fastmnmf_loss_ws(B, N, M, F, T),
                 "fastmnmf_loss_data: workspace too small (ssspy_fastmnmf_loss_workspace_bytes)");
   hipStream_t st = as_stream(stream);

@@ -977,6 +977,8 @@ int ssspy_ip1_source_solve(void *W, const void *U, double *denom, int source_idx
                            int N, int *info, void *stream) {
   SSSPY_REQUIRE(W && U && denom && B > 0 && F > 0, "ip1_source_solve: bad argument");
   SSSPY_REQUIRE(source_idx >= 0 && source_idx < N, "ip1_source_solve: bad source index");
+  if (rt_sources_ok(N))
+    return rt_ip1_source_solve(W, U, denom, source_idx, B, F, N, info, as_stream(stream));
   const long long nbins = (long long)B * F;
   dim3 grid((unsigned)((nbins + 63) / 64)), block(64);
   DISPATCH_N(N, hipLaunchKernelGGL((k_ip1_source_solve<NN>), grid, block, 0, as_stream(stream),

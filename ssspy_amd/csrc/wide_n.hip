@@ -127,6 +127,31 @@ __global__ __launch_bounds__(64) void k_ip1_rt(c128 *W, const c128 *__restrict__
   }
 }
 
+// the solve of source n alone: the unnormalised row conj(w) and d = sqrt(max(Re(w^H U_n w), 0)) per
+// bin (k_ip1_source_solve with the source count at run time)
+__global__ __launch_bounds__(64) void k_ip1_source_solve_rt(c128 *W, const c128 *__restrict__ U,
+                                                            double *__restrict__ denom,
+                                                            long long nbins, int N, int n, int *info) {
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= nbins) return;
+  c128 A[RTN * RTN], w[RTN];
+  const c128 *__restrict__ Wm = W + idx * (N * N);
+  const c128 *__restrict__ Un = U + (idx * N + n) * (long long)(N * N);
+  for (int r = 0; r < N; ++r)
+    for (int c = 0; c < N; ++c) {
+      c128 acc = cmake(0.0, 0.0);
+      for (int k = 0; k < N; ++k) cfma(acc, Wm[r * N + k], Un[k * N + c]);
+      A[r * N + c] = acc;
+    }
+  for (int r = 0; r < N; ++r) w[r] = cmake(r == n ? 1.0 : 0.0, 0.0);
+  const bool ok = rt_lu_solve(A, w, N, 1);
+  double qf = rt_quad(w, Un, N);
+  qf = qf < 0.0 ? 0.0 : qf;  // np.maximum(., 0): NaN propagates
+  denom[idx] = sqrt(qf);
+  for (int c = 0; c < N; ++c) W[idx * (N * N) + n * N + c] = cconj(w[c]);
+  if (!ok && info) atomicAdd(info, 1);
+}
+
 __global__ __launch_bounds__(64) void k_row_power_rt(const c128 *__restrict__ W,
                                                      const c128 *__restrict__ C, double *qbuf,
                                                      long long nbins, int N) {
@@ -348,6 +373,14 @@ int rt_ip1(void *W, const void *U, const void *C, double *qbuf, int B, int F, in
   hipLaunchKernelGGL(k_ip1_rt, dim3((unsigned)((nbins + 63) / 64)), dim3(64), 0, st, (c128 *)W,
                      (const c128 *)U, nbins, N, floor_kind, floor_eps, info, (const c128 *)C, qbuf);
   return check_launch("k_ip1_rt");
+}
+
+int rt_ip1_source_solve(void *W, const void *U, double *denom, int n, int B, int F, int N, int *info,
+                        hipStream_t st) {
+  const long long nbins = (long long)B * F;
+  hipLaunchKernelGGL(k_ip1_source_solve_rt, dim3((unsigned)((nbins + 63) / 64)), dim3(64), 0, st,
+                     (c128 *)W, (const c128 *)U, denom, nbins, N, n, info);
+  return check_launch("k_ip1_source_solve_rt");
 }
 
 int rt_row_power(const void *W, const void *C, double *qbuf, int B, int F, int N, hipStream_t st) {

@@ -11,6 +11,9 @@ int rt_separate(const void *X, const void *W, void *Y, int B, int N, int F, int 
 // C[b, i, s] = (1/T) sum_j w_sj A conj(Bm)^T; Bm == A for the weighted auto-covariance
 int rt_covariance(const void *A, const void *Bm, const double *weight, int kind, void *C, int B,
                   int N, int S, int F, int T, hipStream_t st);
+// IP1 of one source with the floor left to the host (ssspy_ip1_source_solve)
+int rt_ip1_source_solve(void *W, const void *U, double *denom, int n, int B, int F, int N, int *info,
+                        hipStream_t st);
 int rt_ip1(void *W, const void *U, const void *C, double *qbuf, int B, int F, int N, int floor_kind,
            double floor_eps, int *info, hipStream_t st);
 int rt_row_power(const void *W, const void *C, double *qbuf, int B, int F, int N, hipStream_t st);
