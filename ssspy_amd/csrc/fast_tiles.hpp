@@ -43,12 +43,14 @@ __device__ __forceinline__ int tile_pi(int rho) { return 4 * (rho & 3) + (rho >>
 // ---- stage the activation tile V[b, n, 0:KR, j0:j0+16] of every source into LDS rows of VROW
 // doubles (zero beyond K rows / T frames).  256 threads, NS*KR rows * 8 double2 chunks; KR = 16
 // (n_basis <= 16) or 32.
+// FULL: the launcher has checked K == KR and T % 16 == 0 -- every row and frame is in range, no
+// masks or selects (the full-tile instances of the pass kernels, see ilrma_fast.hip).
 template <int NS, int KR = 16>
 struct VStage {
   double2 v[(NS * KR * 8 + 255) / 256];
 };
 
-template <int NS, int KR = 16>
+template <int NS, int KR = 16, bool FULL = false>
 __device__ __forceinline__ void vstage_load(VStage<NS, KR> &st, const double *__restrict__ act_b,
                                             int K, int T, int j0) {
 #pragma unroll
@@ -58,14 +60,16 @@ __device__ __forceinline__ void vstage_load(VStage<NS, KR> &st, const double *__
     const int n = row / KR, k = row % KR;
     const int j = j0 + 2 * chunk;
     double2 val = make_double2(0.0, 0.0);
-#ifdef SSSPY_ASSUME_FULL
-    {
-      const double2_a8 v = *reinterpret_cast<const double2_a8 *>(act_b + ((long long)n * K + k) * T + j);
-      val = make_double2(v.x, v.y);
+    if constexpr (FULL) {
+      // (the idx guard folds away where NS * KR * 8 is a multiple of 256, i.e. NS = 2, 4)
+      if ((NS * KR * 8) % 256 == 0 || idx < NS * KR * 8) {
+        const double2_a8 v =
+            *reinterpret_cast<const double2_a8 *>(act_b + ((long long)n * K + k) * T + j);
+        val = make_double2(v.x, v.y);
+      }
+    } else {
+      if (idx < NS * KR * 8 && k < K) val = load_pair_in_row(act_b + ((long long)n * K + k) * T, j, T);
     }
-#else
-    if (idx < NS * KR * 8 && k < K) val = load_pair_in_row(act_b + ((long long)n * K + k) * T, j, T);
-#endif
     st.v[u] = val;
   }
 }
@@ -267,9 +271,14 @@ __device__ __forceinline__ void xtile_load_transposed(XTile<NC> &xt, const XSrc<
 // the previous tile has been read by everyone / the writes of this one have landed -- so EVERY wave
 // of the workgroup must walk the same tiles.  Halves (NG = 2) the global loads and the LDS writes
 // of the private form; the waves of a bin tile no longer fetch the same lines twice.
-template <int NC, int NG>
-__device__ __forceinline__ void xtile_load_shared(XTile<NC> &xt, const XSrc<NC> &src, int T, int i0,
-                                                  int j0, int c, int q, int g, c128 *patch) {
+// xtile_stage_shared: the fetch and the two barriers only; the tile stays in the patch, frame r of
+// channel m of lane (c, q) at patch[(m * 16 + c) * 17 + q + 4 r].  `between` runs between the two
+// barriers: LDS written there is visible to every wave on return and is no longer read by anyone
+// from the previous tile (the covariance pass passes its weights so).
+template <int NC, int NG, typename Between>
+__device__ __forceinline__ void xtile_stage_shared(const XSrc<NC> &src, int T, int i0, int j0,
+                                                   int c, int q, int g, c128 *patch,
+                                                   Between &&between) {
   static_assert(NC % NG == 0, "channels split evenly over the source groups");
   constexpr int PER = NC / NG;
   const unsigned voff = ((unsigned)(i0 + q) * (unsigned)T + (unsigned)min(j0 + c, T - 1)) * 16u;
@@ -290,7 +299,14 @@ __device__ __forceinline__ void xtile_load_shared(XTile<NC> &xt, const XSrc<NC> 
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr)
       patch[((g * PER + mm) * 16 + 4 * rr + q) * 17 + c] = c128_from(ld[mm][rr]);
+  between();
   __syncthreads();
+}
+
+template <int NC, int NG>
+__device__ __forceinline__ void xtile_load_shared(XTile<NC> &xt, const XSrc<NC> &src, int T, int i0,
+                                                  int j0, int c, int q, int g, c128 *patch) {
+  xtile_stage_shared<NC, NG>(src, T, i0, j0, c, q, g, patch, [] {});
 #pragma unroll
   for (int m = 0; m < NC; ++m)
 #pragma unroll
@@ -328,18 +344,15 @@ __device__ __forceinline__ void xtile_transpose(XTile<NC> &xt, int c, int q, c12
 // GEMM1 of the bin-major tile from the staged V: R[bin c, frame j0+q+4r] in register r
 // (D row q+4r reads slot tile_pi(q+4r) = 4q+r, which holds frame tile_pi(4q+r) = q+4r)
 // ksteps = ceil(K / 4): k-slabs beyond n_basis are zero on both sides and are skipped
-template <int KS>
+// (FULL: K == 4 KS, every slab runs)
+template <int KS, bool FULL = false>
 __device__ __forceinline__ double4_t rt_from_lds(const double *vs_n, const double (&tb)[KS], int c,
                                                  int q, int ksteps) {
   double4_t R = {0.0, 0.0, 0.0, 0.0};
   const int col = tile_pi(c);
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks)
-#ifdef SSSPY_ASSUME_FULL
-    R = mfma_f64(vs_n[(4 * ks + q) * VROW + col], tb[ks], R);
-#else
-    if (ks < ksteps) R = mfma_f64(vs_n[(4 * ks + q) * VROW + col], tb[ks], R);
-#endif
+    if (FULL || ks < ksteps) R = mfma_f64(vs_n[(4 * ks + q) * VROW + col], tb[ks], R);
   return R;
 }
 

@@ -308,40 +308,57 @@ __global__ __launch_bounds__(256) void k_ilrma_activation_finalize(double *act,
 // ------------------------------------------------------------------ power normalisation (filter)
 // psi_n^2 = (1/F) sum_i q[i][n], q[i][n] = Re(w_in C_i w_in^H) = mean_j |y_nij|^2.
 // q comes from the IP1 kernel (fused iteration) or from k_row_power (stand-alone call).
-// grid: (ceil(F/64), B).  Every block folds q over all bins (fixed order: deterministic), then
-// scales the demixing rows and basis rows of its own 64 bins.
+// Two launches: k_norm_psi folds q over all bins once per mixture (fixed order: deterministic) and
+// leaves psi_n in place of q[0][n]; k_norm_scale, grid (ceil(F/64), B), scales the demixing rows
+// and basis rows of its own 64 bins.  (One launch used to fold q in every one of its blocks: the
+// same N values 17 times per mixture at F = 1025, 70 MB of L2 reads at the headline batch.)
+// grid: B; 256 threads
+__global__ __launch_bounds__(256) void k_norm_psi(double *qbuf, int N, int F, int floor_kind,
+                                                  double eps) {
+  __shared__ double wsum[4][SSSPY_RT_MAX_SOURCES];
+  const int b = blockIdx.x;
+  double *qb = qbuf + (long long)b * F * N;
+  // thread t walks the flat (bin, n) array with a stride that keeps its source index fixed
+  const int n = threadIdx.x % N;
+  const int stride = (blockDim.x / N) * N;
+  // (one block per mixture: eight loads in flight per round trip, the per-thread order unchanged --
+  //  adding 0.0 to a sum that started at +0.0 leaves it as it is)
+  double local = 0.0;
+  if ((int)threadIdx.x < stride) {
+    const int total = F * N;
+    for (int e0 = threadIdx.x; e0 < total; e0 += 8 * stride) {
+      double v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = qb[min(e0 + u * stride, total - 1)];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) local += e0 + u * stride < total ? v[u] : 0.0;
+    }
+  }
+  // lanes with equal (lane % N) hold the same source; fold them inside the wave
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int n2 = 0; n2 < N; ++n2) {
+    const double mine = (n == n2) ? local : 0.0;
+    const double tot = wave_sum(mine);
+    if (lane == 0) wsum[wave][n2] = tot;
+  }
+  __syncthreads();  // (every read of q is behind this barrier: psi may overwrite q[0][.])
+  if (threadIdx.x < N) {
+    double v = 0.0;
+    for (int wv = 0; wv < (int)(blockDim.x >> 6); ++wv) v += wsum[wv][threadIdx.x];
+    v = v / (double)F;
+    v = v < 0.0 ? 0.0 : v;
+    qb[threadIdx.x] = apply_floor(sqrt(v), floor_kind, eps);
+  }
+}
+
+// psi of mixture b: qbuf[b F N + n] (k_norm_psi).
 // basis == NULL (partitioning): only W is scaled and psi is published to psi_out (B, N)
 __global__ __launch_bounds__(256) void k_norm_scale(c128 *W, double *basis,
                                                     const double *__restrict__ qbuf, int N, int F,
-                                                    int K, double p, int floor_kind, double eps,
-                                                    double *psi_out) {
-  __shared__ double wsum[4][SSSPY_RT_MAX_SOURCES];
+                                                    int K, double p, double *psi_out) {
   __shared__ double psi[SSSPY_RT_MAX_SOURCES];
   const int b = blockIdx.y;
-  const double *qb = qbuf + (long long)b * F * N;
-  // thread t walks the flat (bin, n) array with a stride that keeps its source index fixed
-  {
-    const int n = threadIdx.x % N;
-    const int stride = (blockDim.x / N) * N;
-    double local = 0.0;
-    if (threadIdx.x < stride)
-      for (int e = threadIdx.x; e < F * N; e += stride) local += qb[e];
-    // lanes with equal (lane % N) hold the same source; fold them inside the wave
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int n2 = 0; n2 < N; ++n2) {
-      const double mine = (n == n2) ? local : 0.0;
-      const double tot = wave_sum(mine);
-      if (lane == 0) wsum[wave][n2] = tot;
-    }
-    __syncthreads();
-    if (threadIdx.x < N) {
-      double v = 0.0;
-      for (int wv = 0; wv < (int)(blockDim.x >> 6); ++wv) v += wsum[wv][threadIdx.x];
-      v = v / (double)F;
-      v = v < 0.0 ? 0.0 : v;
-      psi[threadIdx.x] = apply_floor(sqrt(v), floor_kind, eps);
-    }
-  }
+  if (threadIdx.x < N) psi[threadIdx.x] = qbuf[(long long)b * F * N + threadIdx.x];
   __syncthreads();
   const int i0 = blockIdx.x * 64;
   const int nb = min(64, F - i0);
@@ -1029,10 +1046,15 @@ int ssspy_ilrma_weighted_covariance(const void *X, const void *W, const double *
                    Ysep, Ysep != nullptr, st);
 }
 
-static int launch_norm_scale(void *W, double *basis, const double *qbuf, int B, int N, int F, int K,
-                             double domain, int floor_kind, double floor_eps, hipStream_t st) {
+// qbuf (B, F, N) is consumed: psi replaces its first N values of every mixture (k_norm_psi)
+static int launch_norm_scale(void *W, double *basis, double *qbuf, int B, int N, int F, int K,
+                             double domain, int floor_kind, double floor_eps, hipStream_t st,
+                             double *psi_out = nullptr) {
+  hipLaunchKernelGGL(k_norm_psi, dim3(B), dim3(256), 0, st, qbuf, N, F, floor_kind, floor_eps);
+  int rc = check_launch("k_norm_psi");
+  if (rc) return rc;
   hipLaunchKernelGGL(k_norm_scale, dim3((F + 63) / 64, B), dim3(256), 0, st, (c128 *)W, basis,
-                     qbuf, N, F, K, domain, floor_kind, floor_eps, (double *)nullptr);
+                     (const double *)qbuf, N, F, K, domain, psi_out);
   return check_launch("k_norm_scale");
 }
 
@@ -1441,10 +1463,7 @@ int ssspy_ilrma_partition_normalize(void *W, const void *C, void *Y, double *bas
   if (W) {
     int rc = row_power(W, C, qbuf, B, F, N, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_norm_scale, dim3((F + 63) / 64, B), dim3(256), 0, st, (c128 *)W,
-                       (double *)nullptr, (const double *)qbuf, N, F, K, domain, floor_kind,
-                       floor_eps, psi);
-    rc = check_launch("k_norm_scale");
+    rc = launch_norm_scale(W, nullptr, qbuf, B, N, F, K, domain, floor_kind, floor_eps, st, psi);
     if (rc) return rc;
   } else {
     // (qbuf holds B F N doubles: room for the B N ceil(F / 16) power slots)

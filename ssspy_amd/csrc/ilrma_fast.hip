@@ -94,7 +94,9 @@ enum { IN_Y = 0, IN_X = 1, IN_P = 2 };
 // kernels.  Its 64-register basis operand only fits because |y|^2 of all sources is formed first
 // (the x tile is dead before GEMM1's operands go live); results go to `basis_out` (the sibling
 // item still reads the old basis), which the launcher copies back.
-template <int IN, int MODEL, bool LOSS, int KS>
+// FULL: K == 4 KS and T % 16 == 0 (every k-slab and frame tile full, launcher-checked): no k or
+// frame masks in the walk (bin-edge masks stay).
+template <int IN, int MODEL, bool LOSS, int KS, bool FULL = false>
 __global__ __launch_bounds__(256, KS >= 8 ? 1 : 2) void k_basis_fast(const c128 *__restrict__ X,
                                                        const c128 *__restrict__ W,
                                                        const double *basis, double *basis_out,
@@ -169,7 +171,7 @@ __global__ __launch_bounds__(256, KS >= 8 ? 1 : 2) void k_basis_fast(const c128 
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
         const int kk = 4 * ks + q;
-        tb[n][ks] = kk < K ? basis[(((long long)b * N + n) * F + bin) * K + kk] : 0.0;
+        tb[n][ks] = (FULL || kk < K) ? basis[(((long long)b * N + n) * F + bin) * K + kk] : 0.0;
       }
   }
   double4_t num[N][KTI], den[N][KTI];
@@ -187,7 +189,7 @@ __global__ __launch_bounds__(256, KS >= 8 ? 1 : 2) void k_basis_fast(const c128 
   fast::VStage<N, KR> st;
   XTile cur;
   fast::PTile<N> pcur;
-  fast::vstage_load<N, KR>(st, act_b, K, T, min(jt_begin, ntiles - 1) * 16);
+  fast::vstage_load<N, KR, FULL>(st, act_b, K, T, min(jt_begin, ntiles - 1) * 16);
   fast::vstage_store<N, KR>(st, vs[0]);
   __syncthreads();
 
@@ -207,7 +209,7 @@ __global__ __launch_bounds__(256, KS >= 8 ? 1 : 2) void k_basis_fast(const c128 
       if constexpr (PIN) fast::ptile_load_binmajor<N>(pcur, xsrc, T, bin, j0, q);
       else fast::xtile_load_binmajor<N>(cur, xsrc, T, bin, j0, q);
     }
-    if (KS < 8) fast::vstage_load<N, KR>(st, act_b, K, T, jn);
+    if (KS < 8) fast::vstage_load<N, KR, FULL>(st, act_b, K, T, jn);
     const double *vcur = vs[(jt - jt_begin) & 1];
     double pwall[PWF ? N : 1][4];
     if (PWF) {
@@ -230,7 +232,7 @@ __global__ __launch_bounds__(256, KS >= 8 ? 1 : 2) void k_basis_fast(const c128 
 #pragma unroll
         for (int r = 0; r < 4; ++r) pwall[n][r] = PIN ? pcur.p[n][r] : cabs2(y[r]);
       }
-      if (KS >= 8) fast::vstage_load<N, KR>(st, act_b, K, T, jn);
+      if (KS >= 8) fast::vstage_load<N, KR, FULL>(st, act_b, K, T, jn);
       if constexpr (PREFETCH) {
         const int jnp = fast::pin_after_powers<N>(pwall, jn);
         if constexpr (PIN) fast::ptile_load_binmajor<N>(pcur, xsrc, T, bin, jnp, q);
@@ -241,7 +243,7 @@ __global__ __launch_bounds__(256, KS >= 8 ? 1 : 2) void k_basis_fast(const c128 
     for (int n = 0; n < N; ++n) {
       const double *vn = vcur + n * KR * VROW;
       const double4_t R = TB_LDS ? rt_from_lds(vn, tls[wave] + n * 256, c, q, ksteps)
-                                 : rt_from_lds<KS>(vn, tb[n], c, q, ksteps);
+                                 : rt_from_lds<KS, FULL>(vn, tb[n], c, q, ksteps);
       // GEMM2 B operand: V[n, k = 16 kt + c, frame q + 4r] (slots 4q .. 4q+3 of the permuted row)
       double vb[KTI][4];
 #pragma unroll
@@ -273,11 +275,7 @@ __global__ __launch_bounds__(256, KS >= 8 ? 1 : 2) void k_basis_fast(const c128 
           }
           pw = PIN ? pcur.p[n][r] : cabs2(y);
         }
-#ifdef SSSPY_ASSUME_FULL
-        const bool valid = true;
-#else
-        const bool valid = j0 + q + 4 * r < T;
-#endif
+        const bool valid = FULL || j0 + q + 4 * r < T;
         const double rinv = rcp_nr(R[r]);
         const double bb = valid ? rinv : 0.0;
         const double aa = valid ? mm_num_factor<MODEL>(pw, R[r], rinv, fm) : 0.0;
@@ -524,12 +522,90 @@ constexpr bool WC_SHARE = WC_NG == 2 && N == 4;
 #endif
 static_assert(!WC_SHARE || WC_WB * N * 16 * 17 <= 4 * XPATCH, "shared x patches fit the array");
 
+// Component split of the shared-tile form (N = 4, Gauss at domain 2 or 1): the two waves
+// of a bin tile divide the 16 real components of x x^H between them instead of the sources, so every
+// product is formed once per point.  Wave 0 forms the 4 powers and the (0,1), (2,3) products, wave 1
+// the (0,2), (0,3), (1,2), (1,3) products (16 fp64 VALU each, against 32 for the whole matrix), and
+// each accumulates its half for all four sources: 32 accumulators per lane, as before.  A wave still
+// runs GEMM1 and the reciprocal for its own two sources and hands their weights to the other wave
+// through LDS, between the two barriers of the shared tile fetch.  Each accumulator sees the same
+// fma(phi, z, acc) sequence as in the source split (frames r = 0..3, tiles in order, then the q fold),
+// so U is bitwise the same.
+constexpr int WC_HALF = 8;  // real components per wave
+template <int G>
+__device__ __forceinline__ void wc_half_terms(const c128 (&x)[4], double (&v)[WC_HALF]) {
+  if constexpr (G == 0) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a) v[a] = cabs2(x[a]);
+    const c128 z01 = cmulc(x[0], x[1]), z23 = cmulc(x[2], x[3]);
+    v[4] = z01.x, v[5] = z01.y, v[6] = z23.x, v[7] = z23.y;
+  } else {
+    const c128 z02 = cmulc(x[0], x[2]), z03 = cmulc(x[0], x[3]);
+    const c128 z12 = cmulc(x[1], x[2]), z13 = cmulc(x[1], x[3]);
+    v[0] = z02.x, v[1] = z02.y, v[2] = z03.x, v[3] = z03.y;
+    v[4] = z12.x, v[5] = z12.y, v[6] = z13.x, v[7] = z13.y;
+  }
+}
+
+// one tile of the component split, read frame by frame from LDS: the x tile from the bin tile's
+// patch (xtile_stage_shared), the weights of all four sources from `shared` ([source][r][lane]; the
+// wave's own two are read back too).  Holding the whole x tile or the own weights in registers
+// through the walk costs VGPRs the 2-waves-per-SIMD budget does not have (spills measured).
+template <int G>
+__device__ __forceinline__ void wc_half_tile(double (&acc)[4][WC_HALF], const c128 *patch,
+                                             const double *shared, int lane, int c, int q) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    c128 x[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) x[m] = patch[(m * 16 + c) * 17 + q + 4 * r];
+    double phi[4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n)
+      phi[n] = shared[(n * 4 + r) * 64 + lane];
+    double v[WC_HALF];
+    wc_half_terms<G>(x, v);
+#pragma unroll
+    for (int n = 0; n < 4; ++n)
+#pragma unroll
+      for (int e = 0; e < WC_HALF; ++e) acc[n][e] = fma(phi[n], v[e], acc[n][e]);
+  }
+}
+
+// store of the folded half by the q = 0 lanes (every q-lane holds the sums; spreading the stores over
+// q by source turns the source index into a run-time one and sends the accumulators to scratch)
+template <int G>
+__device__ __forceinline__ void wc_half_store(const double (&acc)[4][WC_HALF], c128 *dst,
+                                              double scale) {
+  constexpr int PA[2][4][2] = {{{0, 1}, {2, 3}, {0, 0}, {0, 0}}, {{0, 2}, {0, 3}, {1, 2}, {1, 3}}};
+  constexpr int NPAIR = G == 0 ? 2 : 4, P0 = G == 0 ? 4 : 0;  // products, first slot of a product
+#pragma unroll
+  for (int n = 0; n < 4; ++n) {
+    c128 *d = dst + n * 16;
+    if constexpr (G == 0) {
+#pragma unroll
+      for (int a = 0; a < 4; ++a) d[a * 4 + a] = cmake(acc[n][a] * scale, 0.0);
+    }
+#pragma unroll
+    for (int p = 0; p < NPAIR; ++p) {
+      const int a = PA[G][p][0], bb = PA[G][p][1];
+      const double zx = acc[n][P0 + 2 * p], zy = acc[n][P0 + 2 * p + 1];
+      d[a * 4 + bb] = cmake(zx * scale, zy * scale);
+      d[bb * 4 + a] = cmake(zx * scale, -zy * scale);
+    }
+  }
+}
+
 // grid: 1-D, see TailPlan.  Unsplit blocks store U directly; split blocks store their partial sums
 // (already scaled by 1/T) to `upart` ([tail item][chunk][WC_BINS][N][N][N]) for k_wcov_fold.
 // t and GGD models: varphi depends on |w_n^H x|^2, so the wave also needs its bins' demixing rows
 // KS: k-steps of GEMM1 compiled in (4: n_basis <= 16, 8: n_basis <= 32; no k tiles here, the pass has
 // no second GEMM)
-template <int MODEL, int KS>
+// FULL: K == 4 KS and T % 16 == 0 (launcher-checked): no k or frame masks in the walk
+// SPLIT (N = 4, Gauss at domain 2 or 1, n_basis <= 16): the waves of a bin tile split x x^H by
+// component (see wc_half_tile); otherwise by source (CovAcc).  Not for t / GGD (their weights need
+// |w_n^H x|^2) nor for the other domains, whose pow weights spill the split form (24 VGPRs).
+template <int MODEL, int KS, bool FULL = false>
 __global__ __launch_bounds__(256, KS >= 16 ? 1 : 2) void k_wcov_fast(const c128 *__restrict__ X,
                                                       const c128 *__restrict__ W,
                                                       const double *__restrict__ basis,
@@ -542,6 +618,9 @@ __global__ __launch_bounds__(256, KS >= 16 ? 1 : 2) void k_wcov_fast(const c128 
   __shared__ __attribute__((aligned(16))) c128 xpatch[4][XPATCH];
   constexpr bool NEEDS_Y = MODEL == FM_T || MODEL == FM_GGD;
   __shared__ __attribute__((aligned(16))) c128 wlc[NEEDS_Y ? 4 * 16 * WSTRIDE : 1];
+  constexpr bool SPLIT = WC_SHARE && !NEEDS_Y && MODEL != FM_GAUSSP && KS == 4;
+  // SPLIT: the weights of every source of each bin tile, [bin tile][source][r][lane]
+  __shared__ __attribute__((aligned(16))) double phis[SPLIT ? WC_WB * N * 4 * 64 : 1];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = lane & 15, q = lane >> 4;
   const BlockWork work = block_work(plan);
@@ -559,7 +638,7 @@ __global__ __launch_bounds__(256, KS >= 16 ? 1 : 2) void k_wcov_fast(const c128 
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       const int kk = 4 * ks + q, n = min(s0 + s, N - 1);
-      tb[s][ks] = kk < K ? basis[(((long long)b * N + n) * F + bin) * K + kk] : 0.0;
+      tb[s][ks] = (FULL || kk < K) ? basis[(((long long)b * N + n) * F + bin) * K + kk] : 0.0;
     }
   c128 *wmine = wlc + (NEEDS_Y ? (wave * 16 + c) * WSTRIDE : 0);
   if (NEEDS_Y) {
@@ -568,8 +647,18 @@ __global__ __launch_bounds__(256, KS >= 16 ? 1 : 2) void k_wcov_fast(const c128 
       wlc[(wave * 16 + bl) * WSTRIDE + rem] = W[((long long)b * F + min(i0 + bl, F - 1)) * (N * N) + rem];
     }
   }
-  CovAcc<N, SG> acc;
-  acc.clear();
+  CovAcc<N, SPLIT ? 1 : SG> acc;  // (SPLIT: hacc instead)
+  double hacc[SPLIT ? 4 : 1][WC_HALF];
+  if constexpr (SPLIT) {
+#pragma unroll
+    for (int n = 0; n < 4; ++n)
+#pragma unroll
+      for (int e = 0; e < WC_HALF; ++e) hacc[n][e] = 0.0;
+  } else {
+    acc.clear();
+  }
+  double *phi_tile = phis + (SPLIT ? wb * (N * 4 * 64) : 0);
+  const int gu = __builtin_amdgcn_readfirstlane(g);
   const int ntiles = (T + 15) >> 4;
   const int tpc = (ntiles + nchunks - 1) / nchunks;
   const int jt_begin = work.chunk * tpc, jt_end = min(ntiles, jt_begin + tpc);
@@ -586,8 +675,41 @@ __global__ __launch_bounds__(256, KS >= 16 ? 1 : 2) void k_wcov_fast(const c128 
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
         const int kk = 4 * ks + q, n = min(s0 + s, N - 1);
-        va[s][ks] = (kk < K && jv < T) ? act_b[((long long)n * K + kk) * T + jv] : 0.0;
+        va[s][ks] = (FULL || (kk < K && jv < T)) ? act_b[((long long)n * K + kk) * T + jv] : 0.0;
       }
+    if constexpr (SPLIT) {
+      // GEMM1 and the weights of the wave's own sources first (no x needed), published with the
+      // x tile: every wave then holds the weights of all four sources for its points
+      double4_t R[SG];
+#pragma unroll
+      for (int s = 0; s < SG; ++s) {
+        R[s] = double4_t{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+          if (FULL || ks < ((K + 3) >> 2)) R[s] = mfma_f64(va[s][ks], tb[s][ks], R[s]);
+      }
+      double own[SG][4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const bool valid = FULL || j0 + q + 4 * r < T;
+#pragma unroll
+        for (int s = 0; s < SG; ++s) {
+          double den = R[s][r];
+          if (MODEL == FM_GAUSS1) den = den * den;  // R^(2/p), p = 1
+          const double ph = MODEL == FM_GAUSSP ? pow_nonneg(den, -fm.pinv2) : rcp_nr(den);
+          own[s][r] = (valid && s0 + s < N) ? ph : 0.0;
+        }
+      }
+      fast::xtile_stage_shared<N, WC_NG>(xsrc, T, i0, j0, c, q, gu, xshare, [&] {
+#pragma unroll
+        for (int s = 0; s < SG; ++s)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) phi_tile[((s0 + s) * 4 + r) * 64 + lane] = own[s][r];
+      });
+      if (gu == 0) wc_half_tile<0>(hacc, xshare, phi_tile, lane, c, q);
+      else wc_half_tile<1>(hacc, xshare, phi_tile, lane, c, q);
+      continue;
+    }
     if constexpr (WC_SHARE) {
       // the two source-group waves of a bin tile fetch HALF of its channels each and exchange them
       // through the tile's LDS patch: every byte of x enters the CU once
@@ -602,11 +724,11 @@ __global__ __launch_bounds__(256, KS >= 16 ? 1 : 2) void k_wcov_fast(const c128 
       R[s] = double4_t{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks)
-        if (ks < ((K + 3) >> 2)) R[s] = mfma_f64(va[s][ks], tb[s][ks], R[s]);
+        if (FULL || ks < ((K + 3) >> 2)) R[s] = mfma_f64(va[s][ks], tb[s][ks], R[s]);
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const bool valid = j0 + q + 4 * r < T;
+      const bool valid = FULL || j0 + q + 4 * r < T;
       c128 x[N];
       double phi[SG];
 #pragma unroll
@@ -631,19 +753,40 @@ __global__ __launch_bounds__(256, KS >= 16 ? 1 : 2) void k_wcov_fast(const c128 
         const double ph = MODEL == FM_GAUSSP ? pow_nonneg(den, -fm.pinv2) : rcp_nr(den);
         phi[s] = (valid && s0 + s < N) ? ph : 0.0;
       }
-      acc.add(x, phi);
+      if constexpr (!SPLIT) acc.add(x, phi);
     }
+  }
+  const double scale = 1.0 / (double)T;
+  const int ob = i0 + c;
+  // (formed only for bins inside F: the address stays within U / upart)
+  auto out_bin = [&]() -> c128 * {
+    return nchunks == 1 ? U + ((long long)b * F + ob) * (long long)(N * N * N)
+                        : upart + (((long long)work.tail_idx * nchunks + work.chunk) * WC_BINS +
+                                   (ob - work.group * WC_BINS)) * (long long)(N * N * N);
+  };
+  if constexpr (SPLIT) {
+    // the 4-way fold over q of CovAcc::fold_q, then every q-lane holds the sums of bin i0+c
+#pragma unroll
+    for (int n = 0; n < 4; ++n)
+#pragma unroll
+      for (int e = 0; e < WC_HALF; ++e) {
+        double v = hacc[n][e];
+        v += __shfl_xor(v, 16, 64);
+        v += __shfl_xor(v, 32, 64);
+        hacc[n][e] = v;
+      }
+    if (ob < F && q == 0) {
+      c128 *dst = out_bin();
+      if (gu == 0) wc_half_store<0>(hacc, dst, scale);
+      else wc_half_store<1>(hacc, dst, scale);
+    }
+    return;
   }
   acc.fold_q();
   // every q-lane holds the full sums of bin i0+c for this wave's SG sources; spread the stores:
   // lane q writes rows a with (a & 3) == q
-  const double scale = 1.0 / (double)T;
-  const int ob = i0 + c;
   if (ob < F) {
-    c128 *dst = nchunks == 1
-                    ? U + ((long long)b * F + ob) * (long long)(N * N * N)
-                    : upart + (((long long)work.tail_idx * nchunks + work.chunk) * WC_BINS +
-                               (ob - work.group * WC_BINS)) * (long long)(N * N * N);
+    c128 *dst = out_bin();
 #pragma unroll
     for (int s = 0; s < SG; ++s) {
       const int n = s0 + s;
@@ -775,7 +918,7 @@ constexpr int trow() {
   return 4 * KS + 1;
 }
 
-template <int KS>
+template <int KS, bool FULL>
 __device__ __forceinline__ void tstage_load(TStage<KS> &st, const double *__restrict__ basis_b,
                                             const c128 *__restrict__ W_b, int F, int K, int i0) {
   constexpr int KR = 4 * KS;
@@ -785,7 +928,7 @@ __device__ __forceinline__ void tstage_load(TStage<KS> &st, const double *__rest
     const int k = idx % KR, bl = (idx / KR) & 15, n = idx / (16 * KR);
     const int bi = i0 + bl;
     double v = 0.0;
-    if (idx < N * 16 * KR && k < K && bi < F) v = basis_b[((long long)n * F + bi) * K + k];
+    if (idx < N * 16 * KR && (FULL || k < K) && bi < F) v = basis_b[((long long)n * F + bi) * K + k];
     st.t[u] = v;
   }
   {
@@ -819,7 +962,8 @@ __device__ __forceinline__ void tstage_store(const TStage<KS> &st, double *tbuf,
 // HAS_W = false: the ISS / IPA state passes the separated spectrogram itself (y = x_n, no filter)
 // KS = 8 / 16 (16 < n_basis <= 32 / 64): grid.y carries (bin chunk, k tile); every k-tile item runs
 // GEMM1 over all k and keeps the sums of its own 16 (see k_basis_fast); one wave per SIMD.
-template <int IN, int MODEL, int KS>
+// FULL: K == 4 KS (launcher-checked): no k masks (see k_basis_fast)
+template <int IN, int MODEL, int KS, bool FULL = false>
 __global__ __launch_bounds__(256, KS >= 8 ? 1 : 2) void k_activation_fast(
     const c128 *__restrict__ X, const c128 *__restrict__ W, const double *__restrict__ basis,
     const double *__restrict__ act, double *__restrict__ part, int F, int T, int K,
@@ -860,7 +1004,7 @@ __global__ __launch_bounds__(256, KS >= 8 ? 1 : 2) void k_activation_fast(
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       const int kk = 4 * ks + q;
-      vb[n][ks] = (kk < K && fvalid) ? act[(((long long)b * N + n) * K + kk) * T + jc] : 0.0;
+      vb[n][ks] = ((FULL || kk < K) && fvalid) ? act[(((long long)b * N + n) * K + kk) * T + jc] : 0.0;
     }
   double4_t numv[N][KTI], denv[N][KTI];
 #pragma unroll
@@ -876,7 +1020,7 @@ __global__ __launch_bounds__(256, KS >= 8 ? 1 : 2) void k_activation_fast(
   TStage<KS> st;
   XTile cur;
   fast::PTile<N> pcur;
-  tstage_load<KS>(st, basis_b, W_b, F, K, t_begin * 16);
+  tstage_load<KS, FULL>(st, basis_b, W_b, F, K, t_begin * 16);
   tstage_store<KS>(st, ts[0], ws[0]);
   __syncthreads();
   for (int it = t_begin; it < t_end; ++it) {
@@ -884,7 +1028,7 @@ __global__ __launch_bounds__(256, KS >= 8 ? 1 : 2) void k_activation_fast(
     const int in = min(it + 1, t_end - 1) * 16;
     if constexpr (PIN) fast::ptile_load_framemajor<N>(pcur, xsrc, T, i0, jc, q);
     else fast::xtile_load_framemajor<N>(cur, xsrc, T, i0, jc, q);
-    tstage_load<KS>(st, basis_b, W_b, F, K, in);
+    tstage_load<KS, FULL>(st, basis_b, W_b, F, K, in);
     const int pb = (it - t_begin) & 1;
     const double *tcur = ts[pb];
     const c128 *wcur = ws[pb];
@@ -895,7 +1039,7 @@ __global__ __launch_bounds__(256, KS >= 8 ? 1 : 2) void k_activation_fast(
       double4_t R = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks)
-        if (ks < ksteps) R = mfma_f64(tn[c * TROW + 4 * ks + q], vb[n][ks], R);
+        if (FULL || ks < ksteps) R = mfma_f64(tn[c * TROW + 4 * ks + q], vb[n][ks], R);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int bl = q + 4 * r;
@@ -965,6 +1109,15 @@ using fast::make_fast_model;
     }                                                       \
   } while (0)
 
+// The full-tile instances (FULL = true) of the three passes: n_basis fills the 4 k-slabs of KS = 4
+// and the frames fill whole 16-frame tiles, so the walks carry no k or frame masks.  Built for the
+// plain Gauss model with a filter only (the headline ILRMA line); every other shape takes the
+// masked form.
+static inline bool full_tiles(int K, int T) { return K == 16 && T % 16 == 0; }
+// The basis pass at 2 sources keeps the masked form: its full instance compiles to 186-192 VGPRs
+// against 146-156, which costs the third wave per SIMD.
+constexpr bool BASIS_FULL = N >= 3;
+
 #if SSSPY_FAST_PART != 2
 // `part` must hold the scratch of ilrma_api.hip's basis_part_bytes() (used only when items are split)
 // loss_out: nullptr, or B zeroed doubles that receive the data term of the loss of the state at entry.
@@ -1010,10 +1163,11 @@ int LAUNCHER(ilrma_fast_basis)(const void *X, const void *W, const double *basis
     const int rc0 = scalar_slots_begin(loss_ws, B, nslots, st);
     if (rc0) return rc0;
   }
-#define SSSPY_BASIS_LAUNCH(HW, M, L, KS_)                                                          \
-  hipLaunchKernelGGL((k_basis_fast<HW, M, L, KS_>), grid, block, 0, st, (const c128 *)X,           \
+#define SSSPY_BASIS_LAUNCH_F(HW, M, L, KS_, FULL_)                                                \
+  hipLaunchKernelGGL((k_basis_fast<HW, M, L, KS_, FULL_>), grid, block, 0, st, (const c128 *)X,    \
                      (const c128 *)W, basis, basis_out, act, F, T, K, floor_kind, eps, plan, part, \
                      fm, loss_slots, slot_stride)
+#define SSSPY_BASIS_LAUNCH(HW, M, L, KS_) SSSPY_BASIS_LAUNCH_F(HW, M, L, KS_, false)
 #define SSSPY_BASIS_LAUNCH_M(HW, L, KS_)                                  \
   switch (fmodel) {                                                       \
     case FM_T: SSSPY_BASIS_LAUNCH(HW, FM_T, false, KS_); break; /* no by-product for the t model */ \
@@ -1042,6 +1196,14 @@ int LAUNCHER(ilrma_fast_basis)(const void *X, const void *W, const double *basis
     } else {
       SSSPY_BASIS_LAUNCH_M(false, false, 8)
     }
+  } else if (BASIS_FULL && W != nullptr && full_tiles(K, T) && fmodel == FM_GAUSS) {
+    if constexpr (BASIS_FULL) {  // (not instantiated at N = 2)
+      if (with_loss) {
+        SSSPY_BASIS_LAUNCH_F(true, FM_GAUSS, true, 4, true);
+      } else {
+        SSSPY_BASIS_LAUNCH_F(true, FM_GAUSS, false, 4, true);
+      }
+    }
   } else if (W != nullptr) {
     if (with_loss) {
       SSSPY_BASIS_LAUNCH_M(true, true, 4)
@@ -1057,6 +1219,7 @@ int LAUNCHER(ilrma_fast_basis)(const void *X, const void *W, const double *basis
   }
 #undef SSSPY_BASIS_LAUNCH_M
 #undef SSSPY_BASIS_LAUNCH
+#undef SSSPY_BASIS_LAUNCH_F
   int rc = check_launch("k_basis_fast");
   if (rc) return rc;
   if (plan.tail > 0) {
@@ -1104,9 +1267,10 @@ int LAUNCHER(ilrma_fast_activation)(const void *X, const void *W, const double *
   const int item_tiles = ktiles == 2 ? 1 : ktiles;  // n_basis <= 32: both k tiles inside the item
 #endif
   dim3 grid((T + 63) / 64, nchunks * item_tiles, B), block(256);
-#define SSSPY_ACT_LAUNCH(HW, M, KS_)                                                             \
-  hipLaunchKernelGGL((k_activation_fast<HW, M, KS_>), grid, block, 0, st, (const c128 *)X,        \
+#define SSSPY_ACT_LAUNCH_F(HW, M, KS_, FULL_)                                                    \
+  hipLaunchKernelGGL((k_activation_fast<HW, M, KS_, FULL_>), grid, block, 0, st, (const c128 *)X, \
                      (const c128 *)W, basis, act, part, F, T, K, tiles_per_chunk, nchunks, fm)
+#define SSSPY_ACT_LAUNCH(HW, M, KS_) SSSPY_ACT_LAUNCH_F(HW, M, KS_, false)
 #define SSSPY_ACT_LAUNCH_M(HW, KS_)                        \
   switch (fmodel) {                                        \
     case FM_T: SSSPY_ACT_LAUNCH(HW, FM_T, KS_); break;     \
@@ -1135,6 +1299,8 @@ int LAUNCHER(ilrma_fast_activation)(const void *X, const void *W, const double *
     } else {
       SSSPY_ACT_LAUNCH_M(false, 8)
     }
+  } else if (W != nullptr && full_tiles(K, T) && fmodel == FM_GAUSS) {
+    SSSPY_ACT_LAUNCH_F(true, FM_GAUSS, 4, true);
   } else if (W != nullptr) {
     SSSPY_ACT_LAUNCH_M(true, 4)
   } else {
@@ -1142,6 +1308,7 @@ int LAUNCHER(ilrma_fast_activation)(const void *X, const void *W, const double *
   }
 #undef SSSPY_ACT_LAUNCH_M
 #undef SSSPY_ACT_LAUNCH
+#undef SSSPY_ACT_LAUNCH_F
   return check_launch("k_activation_fast");
 }
 
@@ -1178,9 +1345,10 @@ int LAUNCHER(ilrma_fast_wcov)(const void *X, const void *W, const double *basis,
                      K > 32 ? 256 : 1024);  // (u_part_bytes(): 1024 records)
   const FastModel fm = make_fast_model(fmodel, mparam, 0, floor_kind, floor_eps);
   dim3 grid(plan.full + plan.tail * plan.split), block(256);
-#define SSSPY_WCOV_LAUNCH(M, KS_)                                                                 \
-  hipLaunchKernelGGL((k_wcov_fast<M, KS_>), grid, block, 0, st, (const c128 *)X, (const c128 *)W,  \
-                     basis, act, (c128 *)U, F, T, K, plan, (c128 *)upart, fm)
+#define SSSPY_WCOV_LAUNCH_F(M, KS_, FULL_)                                                        \
+  hipLaunchKernelGGL((k_wcov_fast<M, KS_, FULL_>), grid, block, 0, st, (const c128 *)X,            \
+                     (const c128 *)W, basis, act, (c128 *)U, F, T, K, plan, (c128 *)upart, fm)
+#define SSSPY_WCOV_LAUNCH(M, KS_) SSSPY_WCOV_LAUNCH_F(M, KS_, false)
 #define SSSPY_WCOV_LAUNCH_M(KS_)                       \
   switch (fmodel) {                                    \
     case FM_T: SSSPY_WCOV_LAUNCH(FM_T, KS_); break;    \
@@ -1193,11 +1361,14 @@ int LAUNCHER(ilrma_fast_wcov)(const void *X, const void *W, const double *basis,
     SSSPY_WCOV_LAUNCH_M(16)
   } else if (K > 16) {
     SSSPY_WCOV_LAUNCH_M(8)
+  } else if (full_tiles(K, T) && fmodel == FM_GAUSS) {
+    SSSPY_WCOV_LAUNCH_F(FM_GAUSS, 4, true);
   } else {
     SSSPY_WCOV_LAUNCH_M(4)
   }
 #undef SSSPY_WCOV_LAUNCH_M
 #undef SSSPY_WCOV_LAUNCH
+#undef SSSPY_WCOV_LAUNCH_F
   int rc = check_launch("k_wcov_fast");
   if (rc || plan.tail == 0) return rc;
   if (split_out && plan.full == 0) {
