@@ -72,9 +72,10 @@ enum { SSSPY_SOURCE_ME = 0x100 };
  * (ssspy_ipa_sweep, ipa_rt.hip, round 6), and so do the Hermitian operators / ssspy_solve (to
  * 16 x 16) and the standalone ssspy_lqpqm2 (to dimension 15; hermitian_rt.hip).  The
  * ssspy_fastmnmf_* entry points take n_channels in [2, 16] and n_sources in [1, 16] (9..16 of either
- * on the run-time forms of fmnmf_rt.hip; SSSPY_ERR_UNSUPPORTED above 16).  The GaussMNMF entry points
- * and the ssspy_ilrma_partition_* entry points (partitioning=True) stay at SSSPY_MAX_SOURCES
- * (SSSPY_ERR_UNSUPPORTED above). */
+ * on the run-time forms of fmnmf_rt.hip; SSSPY_ERR_UNSUPPORTED above 16).  The ssspy_gmnmf_* entry
+ * points take n_sources in [1, 16] at n_channels 2..8 (9..16 sources on the 16-source instantiations
+ * of gmnmf_kernels.hip; SSSPY_ERR_UNSUPPORTED above 16).  The ssspy_ilrma_partition_* entry points
+ * (partitioning=True) stay at SSSPY_MAX_SOURCES (SSSPY_ERR_UNSUPPORTED above). */
 #define SSSPY_RT_MAX_SOURCES 16
 /* n_basis: the kernels walk any number of bases (dense products above 32; checked against the
  * oracle at 1500 and 3000); the bound only keeps 32-bit index arithmetic safe.  Up to round 5: 1024. */
@@ -685,7 +686,10 @@ int ssspy_fastmnmf_separate_eig(const void *X, const void *Q, const double *D, c
 
 /* ------------------------------------------------------------------ GaussMNMF (full-rank SCM)
  * State: basis (B,N,F,K) f64, activation (B,N,K,T) f64, spatial (B,N,F,M,M) c128 Hermitian PSD
- * (the reference's `spatial` (N,F,M,M) with a batch axis).  n_channels M in [2, 8]: one lane per
+ * (the reference's `spatial` (N,F,M,M) with a batch axis).  n_sources N in [1, 16] (above 8 the
+ * per-point kernels run their 16-source instantiations; SSSPY_ERR_UNSUPPORTED above 16, and above 8
+ * sources also when the bin's spatial matrices and basis rows overflow a workgroup's 160 KB of LDS:
+ * n_basis beyond ~600 at 8 channels).  n_channels M in [2, 8]: one lane per
  * (bin, frame) point or per spatial matrix; from 4 channels on the point lives in one packed
  * Hermitian matrix inverted in place (herm_packed.hpp) and the full-storage kernels only redo the
  * blocks whose points leave the fast route of to_psd (flags in the workspace).

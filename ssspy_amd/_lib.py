@@ -21,9 +21,10 @@ PARTITION_LATENT, PARTITION_BASIS, PARTITION_ACTIVATION = 1, 2, 4
 SOURCE_ME = 0x100  # OR-ed into the model: source_algorithm="ME"
 CONTRAST_LAPLACE, CONTRAST_GAUSS, CONTRAST_GAUSS_FIXED = 0, 1, 2
 MAX_PAIRS = 32
-# SSSPY_MAX_SOURCES (per-N kernels: IPA, both MNMF classes, the Hermitian operators; GaussMNMF and
-# the ILRMA partition entry points stop there), SSSPY_RT_MAX_SOURCES (run-time-N kernels: the shared
-# operators, ILRMA, AuxIVA, and FastGaussMNMF's channels and sources), SSSPY_MAX_BASIS
+# SSSPY_MAX_SOURCES (per-N kernels: IPA, both MNMF classes, the Hermitian operators; GaussMNMF's
+# channels and the ILRMA partition entry points stop there), SSSPY_RT_MAX_SOURCES (run-time-N kernels:
+# the shared operators, ILRMA, AuxIVA, FastGaussMNMF's channels and sources, GaussMNMF's sources),
+# SSSPY_MAX_BASIS
 MAX_SOURCES, RT_MAX_SOURCES, MAX_BASIS = 8, 16, 65536
 ABI_VERSION = 3  # SSSPY_ABI_VERSION of the include/ssspy_amd.h these prototypes mirror
 

@@ -26,6 +26,10 @@ int gmnmf_spatial_update_rows(void *H, const double *PQ, long long count, int M,
                               double eps, int *flags, hipStream_t st);
 
 constexpr int GM_NMAX = SSSPY_MAX_SOURCES;
+// 9..16 sources: the per-point kernels below take the source bound NX as a template parameter, GM_NMAX
+// (every shape up to 8 sources, unchanged) or GM_NWIDE (only when N > 8)
+constexpr int GM_NWIDE = SSSPY_RT_MAX_SOURCES;
+static_assert(GM_NWIDE == 2 * GM_NMAX, "the wide forms walk the sources in two groups of GM_NMAX");
 
 // coefficients of XX = c1 x x^H + c0 I after the eigenvalue floor
 __device__ __forceinline__ void xx_floor_coeffs(double s, int floor_kind, double eps, double &c1,
@@ -43,9 +47,9 @@ __device__ __forceinline__ void xx_floor_coeffs(double s, int floor_kind, double
 }
 
 // Per-point state: lambda_n, R^-1 (Hermitian), log det R (both of the floored R), u = R^-1 x.
-template <int M>
+template <int M, int NX = GM_NMAX>
 struct Point {
-  double lam[GM_NMAX];
+  double lam[NX];
   c128 Rinv[M][M];
   double logdet;
   c128 x[M], u[M];
@@ -94,8 +98,8 @@ __device__ __forceinline__ void psd_inverse(c128 (&R)[M][M], c128 (&Rinv)[M][M],
 }
 
 // Hs: spatial matrices of this bin in LDS [n][M*M]; Ts: basis rows of this bin in LDS [n][K]
-template <int M>
-__device__ __forceinline__ void point_setup(Point<M> &pt, const c128 *__restrict__ Xb,
+template <int M, int NX = GM_NMAX>
+__device__ __forceinline__ void point_setup(Point<M, NX> &pt, const c128 *__restrict__ Xb,
                                             const double *__restrict__ act_b, const c128 *Hs,
                                             const double *Ts, int N, int F, int T, int K, int i,
                                             int j, int floor_kind, double eps) {
@@ -104,10 +108,11 @@ __device__ __forceinline__ void point_setup(Point<M> &pt, const c128 *__restrict
   for (int a = 0; a < M; ++a)
 #pragma unroll
     for (int c = 0; c < M; ++c) R[a][c] = cmake(0.0, 0.0);
-#pragma unroll
-  for (int n = 0; n < GM_NMAX; ++n) {
-    double l = 0.0;
-    if (n < N) {
+  if constexpr (NX > GM_NMAX) {
+    // 9..16 sources: a rolled loop, lam not kept (the kernels that need lambda_n form it again, with
+    // the same products in the same order: nothing of it stays live across the inverse)
+    for (int n = 0; n < N; ++n) {
+      double l = 0.0;
       for (int k = 0; k < K; ++k) l = fma(Ts[n * K + k], act_b[((long long)n * K + k) * T + j], l);
 #pragma unroll
       for (int a = 0; a < M; ++a)
@@ -118,7 +123,23 @@ __device__ __forceinline__ void point_setup(Point<M> &pt, const c128 *__restrict
           R[a][c].y = fma(l, h.y, R[a][c].y);
         }
     }
-    pt.lam[n] = l;
+  } else {
+#pragma unroll
+    for (int n = 0; n < NX; ++n) {
+      double l = 0.0;
+      if (n < N) {
+        for (int k = 0; k < K; ++k) l = fma(Ts[n * K + k], act_b[((long long)n * K + k) * T + j], l);
+#pragma unroll
+        for (int a = 0; a < M; ++a)
+#pragma unroll
+          for (int c = 0; c < M; ++c) {
+            const c128 h = Hs[n * M * M + a * M + c];
+            R[a][c].x = fma(l, h.x, R[a][c].x);
+            R[a][c].y = fma(l, h.y, R[a][c].y);
+          }
+      }
+      pt.lam[n] = l;
+    }
   }
   psd_inverse<M>(R, pt.Rinv, pt.logdet, floor_kind, eps);
 #pragma unroll
@@ -150,7 +171,7 @@ __device__ __forceinline__ void stage_bin(c128 *Hs, double *Ts, const c128 *__re
 
 // ------------------------------------------------------------------------------------ traces
 // A[b,n,i,j] = tr(R^-1 XX R^-1 H_n), Bt[b,n,i,j] = tr(R^-1 H_n).  grid: (ceil(T/128), F, B)
-template <int M>
+template <int M, int NX = GM_NMAX>
 __global__ __launch_bounds__(128) void k_gmnmf_traces(const c128 *__restrict__ X,
                                                       const double *__restrict__ basis,
                                                       const double *__restrict__ act,
@@ -167,9 +188,9 @@ __global__ __launch_bounds__(128) void k_gmnmf_traces(const c128 *__restrict__ X
   stage_bin<M>(Hs, Ts, H, basis, b, N, F, K, i);
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= T) return;
-  Point<M> pt;
-  point_setup<M>(pt, X + (long long)b * M * F * T, act + (long long)b * N * K * T, Hs, Ts, N, F, T,
-                 K, i, j, floor_kind, eps);
+  Point<M, NX> pt;
+  point_setup<M, NX>(pt, X + (long long)b * M * F * T, act + (long long)b * N * K * T, Hs, Ts, N, F,
+                     T, K, i, j, floor_kind, eps);
   double s = 0.0;
 #pragma unroll
   for (int m = 0; m < M; ++m) s += cabs2(pt.x[m]);
@@ -437,7 +458,7 @@ __global__ __launch_bounds__(256) void k_gm_part_activation(const double *__rest
 __global__ __launch_bounds__(256) void k_gm_part_latent(const double *__restrict__ raw,
                                                         const double *__restrict__ basis,
                                                         double *latent, int N, int F, int K) {
-  extern __shared__ __attribute__((aligned(16))) double znew[];  // N K doubles (<= 64 KB)
+  extern __shared__ __attribute__((aligned(16))) double znew[];  // N K doubles (<= 128 KB)
   const int b = blockIdx.x;
   for (int e = threadIdx.x; e < N * K; e += blockDim.x) {
     const int n = e / K, k = e % K;
@@ -567,7 +588,15 @@ __device__ __forceinline__ void unpack_hermitian(const double *src, c128 (&A)[M]
     }
 }
 
-template <int M>
+// NX = GM_NWIDE: from 4 channels on (where this kernel only redoes flagged blocks) the sources go in
+// passes of GM_NMAX, each walking the frames again, so the accumulators and the LDS rows stay those
+// of the 8-source form; at 2 and 3 channels one pass takes all 16 weights (5 slots per thread at most).
+template <int M, int NX>
+constexpr int gm_acc_sources() {
+  return (M >= 4 && NX > GM_NMAX) ? GM_NMAX : NX;
+}
+
+template <int M, int NX = GM_NMAX>
 __global__ __launch_bounds__(GM_PB) void k_gmnmf_spatial_acc(const c128 *__restrict__ X,
                                                            const double *__restrict__ basis,
                                                            const double *__restrict__ act,
@@ -577,8 +606,9 @@ __global__ __launch_bounds__(GM_PB) void k_gmnmf_spatial_acc(const c128 *__restr
                                                            double eps,
                                                            const int *__restrict__ flags) {
   if (flags && !flags[blockIdx.y * gridDim.x + blockIdx.x]) return;
+  constexpr int NS = gm_acc_sources<M, NX>();  // sources per pass
   constexpr int E = 2 * M * M;     // packed doubles per point: R^-1 then R^-1 XX R^-1
-  constexpr int ROW = E + GM_NMAX;  // doubles per point in LDS
+  constexpr int ROW = E + NS;      // doubles per point in LDS
   extern __shared__ __attribute__((aligned(16))) char smem[];
   c128 *Hs = reinterpret_cast<c128 *>(smem);
   double *Ts = reinterpret_cast<double *>(Hs + N * M * M);
@@ -587,59 +617,75 @@ __global__ __launch_bounds__(GM_PB) void k_gmnmf_spatial_acc(const c128 *__restr
   stage_bin<M>(Hs, Ts, H, basis, b, N, F, K, i);
   const c128 *Xb = X + (long long)b * M * F * T;
   const double *act_b = act + (long long)b * N * K * T;
-  // accumulators: this thread owns output slots idx = tid, tid + GM_PB, ... of the N*E sums
-  constexpr int SLOTS = (GM_NMAX * E + GM_PB - 1) / GM_PB;
-  double accum[SLOTS];
+  // accumulators: this thread owns output slots idx = tid, tid + GM_PB, ... of the NS*E sums
+  constexpr int SLOTS = (NS * E + GM_PB - 1) / GM_PB;
+  const int passes = NS == NX ? 1 : (N + NS - 1) / NS;
+  for (int pass = 0; pass < passes; ++pass) {
+    const int h0 = pass * NS;                       // first source of the pass
+    const int nh = NS == NX ? N : (N - h0 < NS ? N - h0 : NS);  // sources of the pass
+    double accum[SLOTS];
 #pragma unroll
-  for (int s = 0; s < SLOTS; ++s) accum[s] = 0.0;
-  for (int j0 = 0; j0 < T; j0 += GM_PB) {
-    const int j = j0 + threadIdx.x;
-    double *mine = pts + threadIdx.x * ROW;
-    if (j < T) {
-      Point<M> pt;
-      point_setup<M>(pt, Xb, act_b, Hs, Ts, N, F, T, K, i, j, floor_kind, eps);
-      double s = 0.0;
+    for (int s = 0; s < SLOTS; ++s) accum[s] = 0.0;
+    for (int j0 = 0; j0 < T; j0 += GM_PB) {
+      const int j = j0 + threadIdx.x;
+      double *mine = pts + threadIdx.x * ROW;
+      if (j < T) {
+        Point<M, NX> pt;
+        point_setup<M, NX>(pt, Xb, act_b, Hs, Ts, N, F, T, K, i, j, floor_kind, eps);
+        double s = 0.0;
 #pragma unroll
-      for (int m = 0; m < M; ++m) s += cabs2(pt.x[m]);
-      double c1, c0;
-      xx_floor_coeffs(s, floor_kind, eps, c1, c0);
-      c128 Q[M][M];  // R^-1 XX R^-1 = c1 u u^H + c0 R^-1 R^-1
+        for (int m = 0; m < M; ++m) s += cabs2(pt.x[m]);
+        double c1, c0;
+        xx_floor_coeffs(s, floor_kind, eps, c1, c0);
+        c128 Q[M][M];  // R^-1 XX R^-1 = c1 u u^H + c0 R^-1 R^-1
 #pragma unroll
-      for (int a = 0; a < M; ++a)
+        for (int a = 0; a < M; ++a)
 #pragma unroll
-        for (int c = a; c < M; ++c) {
-          c128 r2 = cmake(0.0, 0.0);
+          for (int c = a; c < M; ++c) {
+            c128 r2 = cmake(0.0, 0.0);
 #pragma unroll
-          for (int k = 0; k < M; ++k) cfma(r2, pt.Rinv[a][k], pt.Rinv[k][c]);
-          const c128 uu = cmulc(pt.u[a], pt.u[c]);
-          Q[a][c] = cmake(fma(c1, uu.x, c0 * r2.x), fma(c1, uu.y, c0 * r2.y));
+            for (int k = 0; k < M; ++k) cfma(r2, pt.Rinv[a][k], pt.Rinv[k][c]);
+            const c128 uu = cmulc(pt.u[a], pt.u[c]);
+            Q[a][c] = cmake(fma(c1, uu.x, c0 * r2.x), fma(c1, uu.y, c0 * r2.y));
+          }
+        pack_hermitian<M>(pt.Rinv, mine);
+        pack_hermitian<M>(Q, mine + M * M);
+        if constexpr (NX == GM_NMAX) {
+#pragma unroll
+          for (int n = 0; n < NX; ++n) mine[E + n] = pt.lam[n];
+        } else {  // lambda of the pass's sources, formed again (point_setup keeps none)
+          for (int q = 0; q < NS; ++q) {
+            const int n = h0 + q;
+            double l = 0.0;
+            if (n < N)
+              for (int k = 0; k < K; ++k)
+                l = fma(Ts[n * K + k], act_b[((long long)n * K + k) * T + j], l);
+            mine[E + q] = l;
+          }
         }
-      pack_hermitian<M>(pt.Rinv, mine);
-      pack_hermitian<M>(Q, mine + M * M);
+      } else {
+        for (int e = 0; e < ROW; ++e) mine[e] = 0.0;
+      }
+      __syncthreads();
 #pragma unroll
-      for (int n = 0; n < GM_NMAX; ++n) mine[E + n] = pt.lam[n];
-    } else {
-      for (int e = 0; e < ROW; ++e) mine[e] = 0.0;
+      for (int s = 0; s < SLOTS; ++s) {
+        const int idx = threadIdx.x + GM_PB * s;
+        if (idx < nh * E) {
+          const int n = idx / E, e = idx % E;
+          double v = accum[s];
+          for (int p = 0; p < GM_PB; ++p) v = fma(pts[p * ROW + E + n], pts[p * ROW + e], v);
+          accum[s] = v;
+        }
+      }
+      __syncthreads();
     }
-    __syncthreads();
 #pragma unroll
     for (int s = 0; s < SLOTS; ++s) {
       const int idx = threadIdx.x + GM_PB * s;
-      if (idx < N * E) {
-        const int n = idx / E, e = idx % E;
-        double v = accum[s];
-        for (int p = 0; p < GM_PB; ++p) v = fma(pts[p * ROW + E + n], pts[p * ROW + e], v);
-        accum[s] = v;
+      if (idx < nh * E) {
+        const int n = h0 + idx / E, e = idx % E;
+        PQacc[(((long long)b * N + n) * F + i) * E + e] = accum[s];
       }
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int s = 0; s < SLOTS; ++s) {
-    const int idx = threadIdx.x + GM_PB * s;
-    if (idx < N * E) {
-      const int n = idx / E, e = idx % E;
-      PQacc[(((long long)b * N + n) * F + i) * E + e] = accum[s];
     }
   }
 }
@@ -729,7 +775,7 @@ __global__ __launch_bounds__(64) void k_gmnmf_normalize(c128 *H, double *basis, 
 
 // ------------------------------------------------------------------------------------- loss
 // out[b] += sum_i mean_j ( tr(R^-1 XX) + log det R ).  grid: (ceil(T/128), F, B)
-template <int M>
+template <int M, int NX = GM_NMAX>
 __global__ __launch_bounds__(128) void k_gmnmf_loss(const c128 *__restrict__ X,
                                                     const double *__restrict__ basis,
                                                     const double *__restrict__ act,
@@ -746,9 +792,9 @@ __global__ __launch_bounds__(128) void k_gmnmf_loss(const c128 *__restrict__ X,
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   double term = 0.0;
   if (j < T) {
-    Point<M> pt;
-    point_setup<M>(pt, X + (long long)b * M * F * T, act + (long long)b * N * K * T, Hs, Ts, N, F,
-                   T, K, i, j, floor_kind, eps);
+    Point<M, NX> pt;
+    point_setup<M, NX>(pt, X + (long long)b * M * F * T, act + (long long)b * N * K * T, Hs, Ts, N,
+                       F, T, K, i, j, floor_kind, eps);
     double s = 0.0, xu = 0.0, trR = 0.0;
 #pragma unroll
     for (int m = 0; m < M; ++m) {
@@ -769,7 +815,9 @@ __global__ __launch_bounds__(128) void k_gmnmf_loss(const c128 *__restrict__ X,
 
 // --------------------------------------------------------------------------- Wiener filter
 // Y[b,n,i,j] = lambda_n (H_n R^-1 x)[ref].  grid: (ceil(T/128), F, B)
-template <int M>
+// NX = GM_NWIDE forms lambda_n again for its output (same products, same order) instead of keeping
+// 16 of them across the inverse
+template <int M, int NX = GM_NMAX>
 __global__ __launch_bounds__(128) void k_gmnmf_separate(const c128 *__restrict__ X,
                                                         const double *__restrict__ basis,
                                                         const double *__restrict__ act,
@@ -792,14 +840,22 @@ __global__ __launch_bounds__(128) void k_gmnmf_separate(const c128 *__restrict__
   double *Ts = reinterpret_cast<double *>(Hs + N * M * M);
   stage_bin<M>(Hs, Ts, H, basis, b, N, F, K, i);
   if (!mine) return;
-  Point<M> pt;
-  point_setup<M>(pt, X + (long long)b * M * F * T, act + (long long)b * N * K * T, Hs, Ts, N, F, T,
-                 K, i, j, floor_kind, eps);
+  Point<M, NX> pt;
+  const double *act_b = act + (long long)b * N * K * T;
+  point_setup<M, NX>(pt, X + (long long)b * M * F * T, act_b, Hs, Ts, N, F, T, K, i, j, floor_kind,
+                     eps);
   for (int n = 0; n < N; ++n) {
     c128 y = cmake(0.0, 0.0);
 #pragma unroll
     for (int c = 0; c < M; ++c) cfma(y, Hs[n * M * M + ref * M + c], pt.u[c]);
-    Y[(((long long)b * N + n) * F + i) * T + j] = cscale(y, pt.lam[n]);
+    double l;
+    if constexpr (NX > GM_NMAX) {
+      l = 0.0;
+      for (int k = 0; k < K; ++k) l = fma(Ts[n * K + k], act_b[((long long)n * K + k) * T + j], l);
+    } else {
+      l = pt.lam[n];
+    }
+    Y[(((long long)b * N + n) * F + i) * T + j] = cscale(y, l);
   }
 }
 
@@ -817,9 +873,9 @@ __global__ __launch_bounds__(128) void k_gmnmf_separate(const c128 *__restrict__
 // in which any point leaves it raises flags[block], and the full-storage kernel of the same name
 // then recomputes exactly the flagged blocks (launched after every *_p kernel; `flags == nullptr`
 // means "all blocks").
-template <int M>
+template <int M, int NX = GM_NMAX>
 struct PointP {
-  double lam[GM_NMAX];
+  double lam[NX];
   HermP<M> Rinv;
   double logdet;
   c128 x[M], u[M];
@@ -827,8 +883,8 @@ struct PointP {
 };
 
 // R^-1, log det, x, u from the accumulated R (shared tail of the two point_setup_p forms)
-template <int M>
-__device__ __forceinline__ void point_finish_p(PointP<M> &pt, const c128 *__restrict__ Xb, int F,
+template <int M, int NX>
+__device__ __forceinline__ void point_finish_p(PointP<M, NX> &pt, const c128 *__restrict__ Xb, int F,
                                                int T, int i, int j, int floor_kind, double eps) {
   if (floor_kind == SSSPY_FLOOR_ADD) {
 #pragma unroll
@@ -845,44 +901,56 @@ __device__ __forceinline__ void point_finish_p(PointP<M> &pt, const c128 *__rest
 // Hb: spatial matrices of this (mixture, bin), source n at Hb + n * hstride (hstride = F M M);
 // Tb: basis rows of this (mixture, bin), source n at Tb + n * tstride (tstride = F K); both uniform
 // over the block
-template <int M>
-__device__ __forceinline__ void point_setup_p(PointP<M> &pt, const c128 *__restrict__ Xb,
+template <int M, int NX = GM_NMAX>
+__device__ __forceinline__ void point_setup_p(PointP<M, NX> &pt, const c128 *__restrict__ Xb,
                                               const double *__restrict__ act_b,
                                               const c128 *__restrict__ Hb, long long hstride,
                                               const double *__restrict__ Tb, long long tstride,
                                               int N, int F, int T, int K, int i, int j,
                                               int floor_kind, double eps) {
   hp_clear<M>(pt.Rinv);
+  auto add = [&](int n, double l) {
+    const c128 *Hn = Hb + n * hstride;
+    const double hl = 0.5 * l;
 #pragma unroll
-  for (int n = 0; n < GM_NMAX; ++n) {
-    double l = 0.0;
-    if (n < N) {
-      for (int k = 0; k < K; ++k)
-        l = fma(Tb[n * tstride + k], act_b[((long long)n * K + k) * T + j], l);
-      const c128 *Hn = Hb + n * hstride;
-      const double hl = 0.5 * l;
+    for (int a = 0; a < M; ++a) {
+      pt.Rinv.d[a] = fma(l, Hn[a * M + a].x, pt.Rinv.d[a]);
 #pragma unroll
-      for (int a = 0; a < M; ++a) {
-        pt.Rinv.d[a] = fma(l, Hn[a * M + a].x, pt.Rinv.d[a]);
-#pragma unroll
-        for (int c = a + 1; c < M; ++c) {
-          const c128 hu = Hn[a * M + c], hd = Hn[c * M + a];
-          c128 &r = pt.Rinv.o[tri<M>(a, c)];
-          r.x = fma(hl, hu.x + hd.x, r.x);
-          r.y = fma(hl, hu.y - hd.y, r.y);
-        }
+      for (int c = a + 1; c < M; ++c) {
+        const c128 hu = Hn[a * M + c], hd = Hn[c * M + a];
+        c128 &r = pt.Rinv.o[tri<M>(a, c)];
+        r.x = fma(hl, hu.x + hd.x, r.x);
+        r.y = fma(hl, hu.y - hd.y, r.y);
       }
     }
-    pt.lam[n] = l;
+  };
+  if constexpr (NX > GM_NMAX) {  // (rolled, lam not kept: as point_setup)
+    for (int n = 0; n < N; ++n) {
+      double l = 0.0;
+      for (int k = 0; k < K; ++k)
+        l = fma(Tb[n * tstride + k], act_b[((long long)n * K + k) * T + j], l);
+      add(n, l);
+    }
+  } else {
+#pragma unroll
+    for (int n = 0; n < NX; ++n) {
+      double l = 0.0;
+      if (n < N) {
+        for (int k = 0; k < K; ++k)
+          l = fma(Tb[n * tstride + k], act_b[((long long)n * K + k) * T + j], l);
+        add(n, l);
+      }
+      pt.lam[n] = l;
+    }
   }
-  point_finish_p<M>(pt, Xb, F, T, i, j, floor_kind, eps);
+  point_finish_p<M, NX>(pt, Xb, F, T, i, j, floor_kind, eps);
 }
 
 // The same from the packed symmetric parts k_gm_pack_spatial leaves per (mixture, bin):
 // Hq[n * M * M + ...] = diagonal Re H_aa, then per upper entry (Re H_ac + Re H_ca, Im H_ac - Im H_ca);
 // sources n >= N hold zeros.  One scalar operand per FMA, no additions, no branches.
-template <int M>
-__device__ __forceinline__ void point_setup_q(PointP<M> &pt, const c128 *__restrict__ Xb,
+template <int M, int NX = GM_NMAX>
+__device__ __forceinline__ void point_setup_q(PointP<M, NX> &pt, const c128 *__restrict__ Xb,
                                               const double *__restrict__ act_b,
                                               const double *__restrict__ Hq,
                                               const double *__restrict__ Tb, long long tstride,
@@ -890,7 +958,7 @@ __device__ __forceinline__ void point_setup_q(PointP<M> &pt, const c128 *__restr
                                               int floor_kind, double eps) {
   hp_clear<M>(pt.Rinv);
 #pragma unroll
-  for (int n = 0; n < GM_NMAX; ++n) {
+  for (int n = 0; n < NX; ++n) {
     double l = 0.0;
     if (n < N) {
       for (int k = 0; k < K; ++k)
@@ -907,19 +975,19 @@ __device__ __forceinline__ void point_setup_q(PointP<M> &pt, const c128 *__restr
     }
     pt.lam[n] = l;
   }
-  point_finish_p<M>(pt, Xb, F, T, i, j, floor_kind, eps);
+  point_finish_p<M, NX>(pt, Xb, F, T, i, j, floor_kind, eps);
 }
 
-// Hq[b, i, n < 8, M M] from H[b, n, i, M, M]; one thread per (b, i, n, slot)
-template <int M>
+// Hq[b, i, n < NX, M M] from H[b, n, i, M, M]; one thread per (b, i, n, slot)
+template <int M, int NX = GM_NMAX>
 __global__ __launch_bounds__(256) void k_gm_pack_spatial(const c128 *__restrict__ H,
                                                          double *__restrict__ Hq, int N, int F,
                                                          long long count) {
   const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= count) return;
   const int slot = (int)(e % (M * M));
-  const int n = (int)((e / (M * M)) % GM_NMAX);
-  const long long bi = e / ((long long)M * M * GM_NMAX);
+  const int n = (int)((e / (M * M)) % NX);
+  const long long bi = e / ((long long)M * M * NX);
   const int i = (int)(bi % F);
   const long long b = bi / F;
   double v = 0.0;
@@ -954,8 +1022,10 @@ __device__ __forceinline__ int flat_block() {
 }
 
 // A, Bt as k_gmnmf_traces, from the packed symmetric parts Hq (k_gm_pack_spatial).
-// NP = 4 or 8: sources compiled in (the padding sources of Hq are zero).  grid: (ceil(T/128), F, B)
-template <int M, int NP>
+// NP = 4 or 8: sources compiled in (the padding sources of Hq are zero).  NX = GM_NWIDE (NP = 8): the
+// point's R^-1 and u serve two groups of 8 sources in turn, each with the accumulators of the 8-source
+// form.  grid: (ceil(T/128), F, B)
+template <int M, int NP, int NX = GM_NMAX>
 __global__ __launch_bounds__(128) void k_gmnmf_traces_p(const c128 *__restrict__ X,
                                                         const double *__restrict__ basis,
                                                         const double *__restrict__ act,
@@ -964,69 +1034,77 @@ __global__ __launch_bounds__(128) void k_gmnmf_traces_p(const c128 *__restrict__
                                                         double *__restrict__ Bt, int N, int F,
                                                         int T, int K, int floor_kind, double eps,
                                                         int *__restrict__ flags) {
+  static_assert(NX == GM_NMAX || NP == GM_NMAX, "the wide form takes groups of 8 sources");
+  constexpr int GROUPS = NX == GM_NMAX ? 1 : NX / NP;
   const int i = blockIdx.y, b = blockIdx.z;
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   const bool live = j < T;
   const int jc = live ? j : T - 1;
-  const double *Hb = Hq + ((long long)b * F + i) * (GM_NMAX * M * M);
-  PointP<M> pt;
-  point_setup_q<M>(pt, X + (long long)b * M * F * T, act + (long long)b * N * K * T, Hb,
-                   basis + ((long long)b * N * F + i) * K, (long long)F * K, N, F, T, K, i, jc,
-                   floor_kind, eps);
+  const double *Hb = Hq + ((long long)b * F + i) * (NX * M * M);
+  PointP<M, NX> pt;
+  point_setup_q<M, NX>(pt, X + (long long)b * M * F * T, act + (long long)b * N * K * T, Hb,
+                       basis + ((long long)b * N * F + i) * K, (long long)F * K, N, F, T, K, i, jc,
+                       floor_kind, eps);
   double s = 0.0;
 #pragma unroll
   for (int m = 0; m < M; ++m) s += cabs2(pt.x[m]);
   double c1, c0;
   xx_floor_coeffs(s, floor_kind, eps, c1, c0);
-  double accA[NP], accB[NP];
+#pragma unroll 1
+  for (int grp = 0; grp < GROUPS; ++grp) {
+    const double *Hg = Hb + grp * (NP * M * M);
+    double accA[NP], accB[NP];
 #pragma unroll
-  for (int n = 0; n < NP; ++n) accA[n] = accB[n] = 0.0;
-  // entry by entry: E = c1 u u^H + c0 R^-2 and G = R^-1, both Hermitian; the entry is formed once
-  // and met with the sources' spatial entries (scalar operands)
+    for (int n = 0; n < NP; ++n) accA[n] = accB[n] = 0.0;
+    // entry by entry: E = c1 u u^H + c0 R^-2 and G = R^-1, both Hermitian; the entry is formed once
+    // and met with the sources' spatial entries (scalar operands)
 #pragma unroll
-  for (int a = 0; a < M; ++a) {
-    const double r2 = c0 != 0.0 ? hp_square_entry<M>(pt.Rinv, a, a).x : 0.0;
-    const double e = fma(c1, cabs2(pt.u[a]), c0 * r2), g = pt.Rinv.d[a];
-#pragma unroll
-    for (int n = 0; n < NP; ++n) {
-      const double h = Hb[n * (M * M) + a];
-      accA[n] = fma(h, e, accA[n]);
-      accB[n] = fma(h, g, accB[n]);
-    }
-  }
-#pragma unroll
-  for (int a = 0; a < M; ++a)
-#pragma unroll
-    for (int c = a + 1; c < M; ++c) {
-      c128 r2 = cmake(0.0, 0.0);
-      if (c0 != 0.0) r2 = hp_square_entry<M>(pt.Rinv, a, c);
-      const c128 uu = cmulc(pt.u[a], pt.u[c]);  // u_a conj(u_c)
-      const double ex = fma(c1, uu.x, c0 * r2.x), ey = fma(c1, uu.y, c0 * r2.y);
-      const c128 g = pt.Rinv.o[tri<M>(a, c)];
-      const int slot = M + 2 * tri<M>(a, c);
+    for (int a = 0; a < M; ++a) {
+      const double r2 = c0 != 0.0 ? hp_square_entry<M>(pt.Rinv, a, a).x : 0.0;
+      const double e = fma(c1, cabs2(pt.u[a]), c0 * r2), g = pt.Rinv.d[a];
 #pragma unroll
       for (int n = 0; n < NP; ++n) {
-        const double hs = Hb[n * (M * M) + slot], hm = Hb[n * (M * M) + slot + 1];
-        accA[n] = fma(ex, hs, accA[n]);
-        accA[n] = fma(ey, hm, accA[n]);
-        accB[n] = fma(g.x, hs, accB[n]);
-        accB[n] = fma(g.y, hm, accB[n]);
+        const double h = Hg[n * (M * M) + a];
+        accA[n] = fma(h, e, accA[n]);
+        accB[n] = fma(h, g, accB[n]);
       }
     }
-  if (live) {
 #pragma unroll
-    for (int n = 0; n < NP; ++n)
-      if (n < N) {
-        const long long o = (((long long)b * N + n) * F + i) * T + j;
-        A[o] = accA[n];
-        Bt[o] = accB[n];
+    for (int a = 0; a < M; ++a)
+#pragma unroll
+      for (int c = a + 1; c < M; ++c) {
+        c128 r2 = cmake(0.0, 0.0);
+        if (c0 != 0.0) r2 = hp_square_entry<M>(pt.Rinv, a, c);
+        const c128 uu = cmulc(pt.u[a], pt.u[c]);  // u_a conj(u_c)
+        const double ex = fma(c1, uu.x, c0 * r2.x), ey = fma(c1, uu.y, c0 * r2.y);
+        const c128 g = pt.Rinv.o[tri<M>(a, c)];
+        const int slot = M + 2 * tri<M>(a, c);
+#pragma unroll
+        for (int n = 0; n < NP; ++n) {
+          const double hs = Hg[n * (M * M) + slot], hm = Hg[n * (M * M) + slot + 1];
+          accA[n] = fma(ex, hs, accA[n]);
+          accA[n] = fma(ey, hm, accA[n]);
+          accB[n] = fma(g.x, hs, accB[n]);
+          accB[n] = fma(g.y, hm, accB[n]);
+        }
       }
+    if (live) {
+#pragma unroll
+      for (int q = 0; q < NP; ++q) {
+        const int n = grp * NP + q;
+        if (n < N) {
+          const long long o = (((long long)b * N + n) * F + i) * T + j;
+          A[o] = accA[q];
+          Bt[o] = accB[q];
+        }
+      }
+    }
   }
   flag_block(pt.ok || !live, flags, flat_block());
 }
 
 // loss slots as k_gmnmf_loss.  grid: (ceil(T/128), F, B)
-template <int M>
+template <int M, int NX = GM_NMAX>
 __global__ __launch_bounds__(128) void k_gmnmf_loss_p(const c128 *__restrict__ X,
                                                       const double *__restrict__ basis,
                                                       const double *__restrict__ act,
@@ -1038,11 +1116,11 @@ __global__ __launch_bounds__(128) void k_gmnmf_loss_p(const c128 *__restrict__ X
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   const bool live = j < T;
   const int jc = live ? j : T - 1;
-  PointP<M> pt;
-  point_setup_p<M>(pt, X + (long long)b * M * F * T, act + (long long)b * N * K * T,
-                   H + ((long long)b * N * F + i) * (M * M), (long long)F * (M * M),
-                   basis + ((long long)b * N * F + i) * K, (long long)F * K, N, F, T, K, i, jc,
-                   floor_kind, eps);
+  PointP<M, NX> pt;
+  point_setup_p<M, NX>(pt, X + (long long)b * M * F * T, act + (long long)b * N * K * T,
+                       H + ((long long)b * N * F + i) * (M * M), (long long)F * (M * M),
+                       basis + ((long long)b * N * F + i) * K, (long long)F * K, N, F, T, K, i, jc,
+                       floor_kind, eps);
   double s = 0.0, xu = 0.0, trR = 0.0;
 #pragma unroll
   for (int m = 0; m < M; ++m) {
@@ -1061,8 +1139,9 @@ __global__ __launch_bounds__(128) void k_gmnmf_loss_p(const c128 *__restrict__ X
 }
 
 // Y as k_gmnmf_separate; a point that leaves the fast route stores NaN in its first source, which
-// the full-storage kernel (launched next with `only_marked`) recomputes.  grid: (ceil(T/128), F, B)
-template <int M>
+// the full-storage kernel (launched next with `only_marked`) recomputes.  NX = GM_NWIDE forms
+// lambda_n again for the output, as k_gmnmf_separate does.  grid: (ceil(T/128), F, B)
+template <int M, int NX = GM_NMAX>
 __global__ __launch_bounds__(128) void k_gmnmf_separate_p(const c128 *__restrict__ X,
                                                           const double *__restrict__ basis,
                                                           const double *__restrict__ act,
@@ -1075,18 +1154,28 @@ __global__ __launch_bounds__(128) void k_gmnmf_separate_p(const c128 *__restrict
   if (j >= T) return;
   const long long hstride = (long long)F * (M * M);
   const c128 *Hb = H + ((long long)b * N * F + i) * (M * M);
-  PointP<M> pt;
-  point_setup_p<M>(pt, X + (long long)b * M * F * T, act + (long long)b * N * K * T, Hb, hstride,
-                   basis + ((long long)b * N * F + i) * K, (long long)F * K, N, F, T, K, i, j,
-                   floor_kind, eps);
+  PointP<M, NX> pt;
+  const double *act_b = act + (long long)b * N * K * T;
+  const double *Tb = basis + ((long long)b * N * F + i) * K;
+  const long long tstride = (long long)F * K;
+  point_setup_p<M, NX>(pt, X + (long long)b * M * F * T, act_b, Hb, hstride, Tb, tstride, N, F, T,
+                       K, i, j, floor_kind, eps);
   const double nan = __builtin_nan("");
 #pragma unroll
-  for (int n = 0; n < GM_NMAX; ++n)
+  for (int n = 0; n < NX; ++n)
     if (n < N) {
       c128 y = cmake(0.0, 0.0);
 #pragma unroll
       for (int c = 0; c < M; ++c) cfma(y, Hb[n * hstride + ref * M + c], pt.u[c]);
-      y = cscale(y, pt.lam[n]);
+      double l;
+      if constexpr (NX > GM_NMAX) {
+        l = 0.0;
+        for (int k = 0; k < K; ++k)
+          l = fma(Tb[n * tstride + k], act_b[((long long)n * K + k) * T + j], l);
+      } else {
+        l = pt.lam[n];
+      }
+      y = cscale(y, l);
       if (n == 0 && !pt.ok) y = cmake(nan, nan);
       Y[(((long long)b * N + n) * F + i) * T + j] = y;
     }
@@ -1102,18 +1191,22 @@ __global__ __launch_bounds__(128) void k_gmnmf_separate_p(const c128 *__restrict
 constexpr int GM_SPLIT_FROM = 4;  // channels from which the two matrices take turns in the rows
 constexpr int gm_pow2_floor(int v) { return v >= 8 ? 8 : (v >= 4 ? 4 : (v >= 2 ? 2 : 1)); }
 
-template <int EW>  // value slots per row (even); the N weights follow at EW .. EW + 7
+// NX = GM_NWIDE: 16 weights per row, so NPT doubles: 2 at 4 channels, 4 at 5, 8 at 6-8 (32
+// accumulators over the two matrices of the split rows); a row of 8 channels takes 81 doubles, 41.5 KB
+// per workgroup.
+// EW: value slots per row (even); the NX weights follow at EW .. EW + NX - 1
+template <int EW, int NX = GM_NMAX>
 struct GmFold {
   static constexpr int EG = EW / 2;
   static constexpr int NG = gm_pow2_floor(64 / EG);
-  static constexpr int NPT = GM_NMAX / NG;
-  static constexpr int ROW = EW + GM_NMAX + 1;  // odd: rows of neighbouring lanes on distinct banks
+  static constexpr int NPT = NX / NG;
+  static constexpr int ROW = EW + NX + 1;  // odd: rows of neighbouring lanes on distinct banks
 };
 
-template <int EW>
+template <int EW, int NX = GM_NMAX>
 __device__ __forceinline__ void gm_fold_chunk(const double *pts,
-                                              double (&acc)[GmFold<EW>::NPT][2]) {
-  using S = GmFold<EW>;
+                                              double (&acc)[GmFold<EW, NX>::NPT][2]) {
+  using S = GmFold<EW, NX>;
   const int eg = threadIdx.x % S::EG, ng = threadIdx.x / S::EG;
   if (ng >= S::NG) return;
   const double *v = pts + 2 * eg, *l = pts + EW + ng * S::NPT;
@@ -1128,11 +1221,11 @@ __device__ __forceinline__ void gm_fold_chunk(const double *pts,
   }
 }
 
-template <int EW>
-__device__ __forceinline__ void gm_fold_store(const double (&acc)[GmFold<EW>::NPT][2],
+template <int EW, int NX = GM_NMAX>
+__device__ __forceinline__ void gm_fold_store(const double (&acc)[GmFold<EW, NX>::NPT][2],
                                               double *__restrict__ dst, int N, int limit,
                                               long long nstride) {
-  using S = GmFold<EW>;
+  using S = GmFold<EW, NX>;
   const int eg = threadIdx.x % S::EG, ng = threadIdx.x / S::EG;
   if (ng >= S::NG) return;
 #pragma unroll
@@ -1145,7 +1238,7 @@ __device__ __forceinline__ void gm_fold_store(const double (&acc)[GmFold<EW>::NP
   }
 }
 
-template <int M>
+template <int M, int NX = GM_NMAX>
 __global__ __launch_bounds__(GM_PB) void k_gmnmf_spatial_acc_p(const c128 *__restrict__ X,
                                                              const double *__restrict__ basis,
                                                              const double *__restrict__ act,
@@ -1156,7 +1249,7 @@ __global__ __launch_bounds__(GM_PB) void k_gmnmf_spatial_acc_p(const c128 *__res
   constexpr bool SPLIT = M >= GM_SPLIT_FROM;
   constexpr int MM2 = M * M;
   constexpr int EW = SPLIT ? ((MM2 + 1) & ~1) : 2 * MM2;  // value slots per row
-  using S = GmFold<EW>;
+  using S = GmFold<EW, NX>;
   constexpr int ROW = S::ROW;
   constexpr int PASSES = SPLIT ? 2 : 1;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1164,7 +1257,7 @@ __global__ __launch_bounds__(GM_PB) void k_gmnmf_spatial_acc_p(const c128 *__res
   const int i = blockIdx.x, b = blockIdx.y;
   const c128 *Xb = X + (long long)b * M * F * T;
   const double *act_b = act + (long long)b * N * K * T;
-  const double *Hb = Hq + ((long long)b * F + i) * (GM_NMAX * M * M);
+  const double *Hb = Hq + ((long long)b * F + i) * (NX * M * M);
   const double *Tb = basis + ((long long)b * N * F + i) * K;
   double acc[PASSES][S::NPT][2];
 #pragma unroll
@@ -1176,9 +1269,9 @@ __global__ __launch_bounds__(GM_PB) void k_gmnmf_spatial_acc_p(const c128 *__res
   for (int j0 = 0; j0 < T; j0 += GM_PB) {
     const int j = j0 + threadIdx.x;
     const bool live = j < T;
-    PointP<M> pt;
-    point_setup_q<M>(pt, Xb, act_b, Hb, Tb, (long long)F * K, N, F, T, K, i, live ? j : T - 1,
-                     floor_kind, eps);
+    PointP<M, NX> pt;
+    point_setup_q<M, NX>(pt, Xb, act_b, Hb, Tb, (long long)F * K, N, F, T, K, i, live ? j : T - 1,
+                         floor_kind, eps);
     all_ok = all_ok && (pt.ok || !live);
     double s = 0.0;
 #pragma unroll
@@ -1195,11 +1288,11 @@ __global__ __launch_bounds__(GM_PB) void k_gmnmf_spatial_acc_p(const c128 *__res
     }
     if (SPLIT && (MM2 & 1)) mine[MM2] = 0.0;
 #pragma unroll
-    for (int n = 0; n < GM_NMAX; ++n) mine[EW + n] = live ? pt.lam[n] : 0.0;
+    for (int n = 0; n < NX; ++n) mine[EW + n] = live ? pt.lam[n] : 0.0;
     constexpr int QOFF = SPLIT ? 0 : MM2;  // where packed Q = c1 u u^H + c0 R^-2 goes
     if (SPLIT) {
       __syncthreads();
-      gm_fold_chunk<EW>(pts, acc[0]);
+      gm_fold_chunk<EW, NX>(pts, acc[0]);
       __syncthreads();
     }
 #pragma unroll
@@ -1219,16 +1312,16 @@ __global__ __launch_bounds__(GM_PB) void k_gmnmf_spatial_acc_p(const c128 *__res
         mine[QOFF + e + 1] = fma(c1, uu.y, c0 * r2.y);
       }
     __syncthreads();
-    gm_fold_chunk<EW>(pts, acc[PASSES - 1]);
+    gm_fold_chunk<EW, NX>(pts, acc[PASSES - 1]);
     __syncthreads();
   }
   double *dst = PQacc + ((long long)b * N * F + i) * (2 * MM2);
   const long long nstride = (long long)F * (2 * MM2);
   if (SPLIT) {
-    gm_fold_store<EW>(acc[0], dst, N, MM2, nstride);
-    gm_fold_store<EW>(acc[PASSES - 1], dst + MM2, N, MM2, nstride);
+    gm_fold_store<EW, NX>(acc[0], dst, N, MM2, nstride);
+    gm_fold_store<EW, NX>(acc[PASSES - 1], dst + MM2, N, MM2, nstride);
   } else {
-    gm_fold_store<EW>(acc[0], dst, N, 2 * MM2, nstride);
+    gm_fold_store<EW, NX>(acc[0], dst, N, 2 * MM2, nstride);
   }
   flag_block(all_ok, flags, blockIdx.y * gridDim.x + blockIdx.x);
 }
@@ -1508,6 +1601,9 @@ static inline int gm_act_chunks(int B, int N, int F, int T) {
   if (want > (F + 7) / 8) want = (F + 7) / 8;  // at least 8 bins per chunk
   return want < 1 ? 1 : (int)want;
 }
+// source slots per bin of the packed spatial parts Hq (and the NX of the per-point kernels)
+static inline int gm_nx(int N) { return N > GM_NMAX ? GM_NWIDE : GM_NMAX; }
+
 static inline GmnmfWs gmnmf_ws(int B, int N, int M, int F, int T, int K) {
   GmnmfWs w;
   size_t off = 0;
@@ -1535,8 +1631,8 @@ static inline GmnmfWs gmnmf_ws(int B, int N, int M, int F, int T, int K) {
   }
   w.flags = off;  // one int per block of the per-point kernels: left the fast route (packed path)
   off += align256((size_t)((T + 127) / 128) * F * B * sizeof(int));
-  w.hq = off;  // packed symmetric parts of the spatial matrices, [b][i][8][M M] (packed path)
-  off += align256((size_t)B * F * GM_NMAX * M * M * sizeof(double));
+  w.hq = off;  // packed symmetric parts of the spatial matrices, [b][i][gm_nx(N)][M M] (packed path)
+  off += align256((size_t)B * F * gm_nx(N) * M * M * sizeof(double));
   w.total = off;
   return w;
 }
@@ -1545,23 +1641,61 @@ static inline size_t bin_smem(int N, int M, int K) {
   return (size_t)N * M * M * sizeof(c128) + (size_t)((N * K + 1) & ~1) * sizeof(double);
 }
 
-#define GM_DISPATCH_M(M_, CALL)                                                              \
+// (variadic: GM_DISPATCH_MN hands it a call already expanded, commas and all)
+#define GM_DISPATCH_M(M_, ...)                                                               \
   switch (M_) {                                                                              \
-    case 2: { constexpr int MM = 2; CALL; } break;                                           \
-    case 3: { constexpr int MM = 3; CALL; } break;                                           \
-    case 4: { constexpr int MM = 4; CALL; } break;                                           \
-    case 5: { constexpr int MM = 5; CALL; } break;                                           \
-    case 6: { constexpr int MM = 6; CALL; } break;                                           \
-    case 7: { constexpr int MM = 7; CALL; } break;                                           \
-    case 8: { constexpr int MM = 8; CALL; } break;                                           \
+    case 2: { constexpr int MM = 2; __VA_ARGS__; } break;                                    \
+    case 3: { constexpr int MM = 3; __VA_ARGS__; } break;                                    \
+    case 4: { constexpr int MM = 4; __VA_ARGS__; } break;                                    \
+    case 5: { constexpr int MM = 5; __VA_ARGS__; } break;                                    \
+    case 6: { constexpr int MM = 6; __VA_ARGS__; } break;                                    \
+    case 7: { constexpr int MM = 7; __VA_ARGS__; } break;                                    \
+    case 8: { constexpr int MM = 8; __VA_ARGS__; } break;                                    \
     default: return fail(SSSPY_ERR_UNSUPPORTED, "GaussMNMF: n_channels must be in [2, 8]");  \
   }
 
+// 9..16 sources, the NX = GM_NWIDE instantiations
+#define GM_DISPATCH_MN(M_, N_, ...)    \
+  if ((N_) > GM_NMAX) {                \
+    constexpr int NX = GM_NWIDE;       \
+    GM_DISPATCH_M(M_, __VA_ARGS__);    \
+  } else {                             \
+    constexpr int NX = GM_NMAX;        \
+    GM_DISPATCH_M(M_, __VA_ARGS__);    \
+  }
+
+constexpr size_t GM_LDS_MAX = 160 * 1024;  // LDS a workgroup may take on gfx950
+
+static int lds_attribute(const void *fn, size_t bytes) {
+  if (bytes <= 48 * 1024) return SSSPY_OK;
+  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  return e == hipSuccess ? SSSPY_OK : fail(SSSPY_ERR_HIP, hipGetErrorString(e));
+}
+
 static int check_dims(int B, int N, int M, int F, int T, int K) {
   SSSPY_REQUIRE(B > 0 && F > 0 && T > 0, "GaussMNMF: bad shape");
-  SSSPY_REQUIRE(N >= 1 && N <= SSSPY_MAX_SOURCES, "GaussMNMF: n_sources must be in [1, 8]");
+  SSSPY_REQUIRE(N >= 1, "GaussMNMF: n_sources must be in [1, 16]");
+  if (N > GM_NWIDE) return fail(SSSPY_ERR_UNSUPPORTED, "GaussMNMF: n_sources must be in [1, 16]");
   SSSPY_REQUIRE(K >= 1 && K <= SSSPY_MAX_BASIS, "GaussMNMF: n_basis must be in [1, 65536]");
   if (M < 2 || M > 8) return fail(SSSPY_ERR_UNSUPPORTED, "GaussMNMF: n_channels must be in [2, 8]");
+  if (N > GM_NMAX) {
+    // the full-storage kernels stage the bin's N spatial matrices and N basis rows in LDS; the
+    // spatial sums add a row per frame of the chunk (k_gmnmf_spatial_acc)
+    const int ns = M >= 4 ? GM_NMAX : GM_NWIDE;
+    const size_t acc = bin_smem(N, M, K) + (size_t)GM_PB * (2 * M * M + ns) * sizeof(double);
+    if (acc > GM_LDS_MAX)
+      return fail(SSSPY_ERR_UNSUPPORTED,
+                  "GaussMNMF: above 8 sources n_basis is bounded by the 160 KB of LDS of a "
+                  "workgroup (the bin's spatial matrices and basis rows)");
+    int rc = SSSPY_OK;
+    const size_t bin = bin_smem(N, M, K);
+    GM_DISPATCH_M(M, {
+      rc = lds_attribute((const void *)k_gmnmf_traces<MM, GM_NWIDE>, bin);
+      if (!rc) rc = lds_attribute((const void *)k_gmnmf_loss<MM, GM_NWIDE>, bin);
+      if (!rc) rc = lds_attribute((const void *)k_gmnmf_separate<MM, GM_NWIDE>, bin);
+    });
+    if (rc) return rc;
+  }
   return SSSPY_OK;
 }
 
@@ -1572,10 +1706,10 @@ static bool packed_points(int M) { return M >= 4; }
 
 static int launch_pack_spatial(const void *H, double *Hq, int B, int N, int M, int F,
                                hipStream_t st) {
-  const long long count = (long long)B * F * GM_NMAX * M * M;
-  GM_DISPATCH_M(M, hipLaunchKernelGGL((k_gm_pack_spatial<MM>),
-                                      dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st,
-                                      (const c128 *)H, Hq, N, F, count));
+  const long long count = (long long)B * F * gm_nx(N) * M * M;
+  GM_DISPATCH_MN(M, N, hipLaunchKernelGGL((k_gm_pack_spatial<MM, NX>),
+                                          dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st,
+                                          (const c128 *)H, Hq, N, F, count));
   return check_launch("k_gm_pack_spatial");
 }
 
@@ -1595,17 +1729,22 @@ static int launch_traces(const void *X, const double *basis, const double *act, 
       GM_DISPATCH_M(M, hipLaunchKernelGGL((k_gmnmf_traces_p<MM, 4>), grid, block, 0, st,
                                           (const c128 *)X, basis, act, (const double *)Hq, A, Bt,
                                           N, F, T, K, floor_kind, eps, flags));
-    } else {
+    } else if (N <= GM_NMAX) {
       GM_DISPATCH_M(M, hipLaunchKernelGGL((k_gmnmf_traces_p<MM, 8>), grid, block, 0, st,
+                                          (const c128 *)X, basis, act, (const double *)Hq, A, Bt,
+                                          N, F, T, K, floor_kind, eps, flags));
+    } else {
+      GM_DISPATCH_M(M, hipLaunchKernelGGL((k_gmnmf_traces_p<MM, 8, GM_NWIDE>), grid, block, 0, st,
                                           (const c128 *)X, basis, act, (const double *)Hq, A, Bt,
                                           N, F, T, K, floor_kind, eps, flags));
     }
     rc = check_launch("k_gmnmf_traces_p");
     if (rc) return rc;
   }
-  GM_DISPATCH_M(M, hipLaunchKernelGGL((k_gmnmf_traces<MM>), grid, block, bin_smem(N, M, K), st,
-                                      (const c128 *)X, basis, act, (const c128 *)H, A, Bt, N, F, T,
-                                      K, floor_kind, eps, packed ? (const int *)flags : nullptr));
+  GM_DISPATCH_MN(M, N, hipLaunchKernelGGL((k_gmnmf_traces<MM, NX>), grid, block,
+                                          bin_smem(N, M, K), st, (const c128 *)X, basis, act,
+                                          (const c128 *)H, A, Bt, N, F, T, K, floor_kind, eps,
+                                          packed ? (const int *)flags : nullptr));
   return check_launch("k_gmnmf_traces");
 }
 
@@ -1715,19 +1854,20 @@ int ssspy_gmnmf_update(const void *X, double *basis, double *activation, double 
   if (steps & SSSPY_GMNMF_SPATIAL) {
     rc = refresh();
     if (rc) return rc;
-    const size_t smem = bin_smem(N, M, K) + (size_t)GM_PB * (2 * M * M + GM_NMAX) * sizeof(double);
-    GM_DISPATCH_M(M, {
+    GM_DISPATCH_MN(M, N, {
+      const size_t smem = bin_smem(N, M, K) +
+                          (size_t)GM_PB * (2 * MM * MM + gm_acc_sources<MM, NX>()) * sizeof(double);
       if (smem > 48 * 1024) {  // 8 channels: 64 points x 136 doubles; gfx950 has 160 KB per CU
-        hipError_t e = hipFuncSetAttribute((const void *)k_gmnmf_spatial_acc<MM>,
+        hipError_t e = hipFuncSetAttribute((const void *)k_gmnmf_spatial_acc<MM, NX>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e != hipSuccess) return fail(SSSPY_ERR_HIP, hipGetErrorString(e));
       }
       const bool packed = packed_points(M);
       if (packed) {
         const int ew_p = MM >= GM_SPLIT_FROM ? ((MM * MM + 1) & ~1) : 2 * MM * MM;
-        const size_t smem_p = (size_t)GM_PB * (ew_p + GM_NMAX + 1) * sizeof(double);
+        const size_t smem_p = (size_t)GM_PB * (ew_p + NX + 1) * sizeof(double);
         if (smem_p > 48 * 1024) {
-          hipError_t e = hipFuncSetAttribute((const void *)k_gmnmf_spatial_acc_p<MM>,
+          hipError_t e = hipFuncSetAttribute((const void *)k_gmnmf_spatial_acc_p<MM, NX>,
                                              hipFuncAttributeMaxDynamicSharedMemorySize,
                                              (int)smem_p);
           if (e != hipSuccess) return fail(SSSPY_ERR_HIP, hipGetErrorString(e));
@@ -1735,11 +1875,11 @@ int ssspy_gmnmf_update(const void *X, double *basis, double *activation, double 
         if (!hq_valid) rc = launch_pack_spatial(spatial, Hq, B, N, M, F, st);
         if (rc) return rc;
         hq_valid = true;
-        hipLaunchKernelGGL((k_gmnmf_spatial_acc_p<MM>), dim3(F, B), dim3(GM_PB), smem_p, st,
+        hipLaunchKernelGGL((k_gmnmf_spatial_acc_p<MM, NX>), dim3(F, B), dim3(GM_PB), smem_p, st,
                            (const c128 *)X, Tn, Vn, (const double *)Hq, PQ, N, F, T, K,
                            floor_kind, floor_eps, flags);
       }
-      hipLaunchKernelGGL((k_gmnmf_spatial_acc<MM>), dim3(F, B), dim3(GM_PB), smem, st,
+      hipLaunchKernelGGL((k_gmnmf_spatial_acc<MM, NX>), dim3(F, B), dim3(GM_PB), smem, st,
                          (const c128 *)X, Tn, Vn, (const c128 *)spatial, PQ, N, F, T, K,
                          floor_kind, floor_eps, packed ? (const int *)flags : nullptr);
     });
@@ -1800,7 +1940,10 @@ int ssspy_gmnmf_update(const void *X, double *basis, double *activation, double 
       return fail(SSSPY_ERR_UNSUPPORTED, "GaussMNMF: partitioning takes n_basis up to 1024");
     rc = basis_sums(raw);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_gm_part_latent, dim3(B), dim3(256), (size_t)N * K * sizeof(double), st,
+    const size_t smem_z = (size_t)N * K * sizeof(double);  // up to 128 KB at 16 sources
+    rc = lds_attribute((const void *)k_gm_part_latent, smem_z);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_gm_part_latent, dim3(B), dim3(256), smem_z, st,
                        (const double *)raw,
                        (const double *)basis, latent, N, F, K);
     rc = check_launch("k_gm_part_latent");
@@ -1831,17 +1974,18 @@ int ssspy_gmnmf_loss(const void *X, const double *basis, const double *activatio
   int *flags = (int *)((char *)workspace + align256(scalar_slots_bytes(B, (int)grid.x * F)));
   const bool packed = packed_points(M);
   if (packed) {
-    GM_DISPATCH_M(M, hipLaunchKernelGGL((k_gmnmf_loss_p<MM>), grid, block, 0, st, (const c128 *)X,
-                                        basis, activation, (const c128 *)spatial,
-                                        (double *)workspace, N, F, T, K, floor_kind, floor_eps,
-                                        flags));
+    GM_DISPATCH_MN(M, N, hipLaunchKernelGGL((k_gmnmf_loss_p<MM, NX>), grid, block, 0, st,
+                                            (const c128 *)X, basis, activation,
+                                            (const c128 *)spatial, (double *)workspace, N, F, T,
+                                            K, floor_kind, floor_eps, flags));
     rc = check_launch("k_gmnmf_loss_p");
     if (rc) return rc;
   }
-  GM_DISPATCH_M(M, hipLaunchKernelGGL((k_gmnmf_loss<MM>), grid, block, bin_smem(N, M, K), st,
-                                      (const c128 *)X, basis, activation, (const c128 *)spatial,
-                                      (double *)workspace, N, F, T, K, floor_kind, floor_eps,
-                                      packed ? (const int *)flags : nullptr));
+  GM_DISPATCH_MN(M, N, hipLaunchKernelGGL((k_gmnmf_loss<MM, NX>), grid, block,
+                                          bin_smem(N, M, K), st, (const c128 *)X, basis,
+                                          activation, (const c128 *)spatial, (double *)workspace,
+                                          N, F, T, K, floor_kind, floor_eps,
+                                          packed ? (const int *)flags : nullptr));
   rc = check_launch("k_gmnmf_loss");
   return rc ? rc : scalar_slots_fold(workspace, B, (int)grid.x * F, out, 0, st);
 }
@@ -1856,17 +2000,18 @@ int ssspy_gmnmf_separate(const void *X, const double *basis, const double *activ
   dim3 grid((T + 127) / 128, F, B), block(128);
   const bool packed = packed_points(M);
   if (packed) {
-    GM_DISPATCH_M(M, hipLaunchKernelGGL((k_gmnmf_separate_p<MM>), grid, block, 0,
-                                        as_stream(stream), (const c128 *)X, basis, activation,
-                                        (const c128 *)spatial, (c128 *)Y, N, F, T, K,
-                                        reference_id, floor_kind, floor_eps));
+    GM_DISPATCH_MN(M, N, hipLaunchKernelGGL((k_gmnmf_separate_p<MM, NX>), grid, block, 0,
+                                            as_stream(stream), (const c128 *)X, basis, activation,
+                                            (const c128 *)spatial, (c128 *)Y, N, F, T, K,
+                                            reference_id, floor_kind, floor_eps));
     rc = check_launch("k_gmnmf_separate_p");
     if (rc) return rc;
   }
-  GM_DISPATCH_M(M, hipLaunchKernelGGL((k_gmnmf_separate<MM>), grid, block, bin_smem(N, M, K),
-                                      as_stream(stream), (const c128 *)X, basis, activation,
-                                      (const c128 *)spatial, (c128 *)Y, N, F, T, K, reference_id,
-                                      floor_kind, floor_eps, packed ? 1 : 0));
+  GM_DISPATCH_MN(M, N, hipLaunchKernelGGL((k_gmnmf_separate<MM, NX>), grid, block,
+                                          bin_smem(N, M, K), as_stream(stream), (const c128 *)X,
+                                          basis, activation, (const c128 *)spatial, (c128 *)Y, N,
+                                          F, T, K, reference_id, floor_kind, floor_eps,
+                                          packed ? 1 : 0));
   return check_launch("k_gmnmf_separate");
 }
 
