@@ -554,6 +554,35 @@ int ssspy_iva_weight(const double *r2, double *weight, double *variance, int B, 
 int ssspy_iva_loss_data(const double *r2, const double *variance, double *out, int B, int N, int F,
                         int T, int contrast, void *stream);
 
+/* ------------------------------------------------- gradient / natural-gradient IVA */
+
+/* Score weights phi[b,n,j] of the Laplace / Gauss gradient classes from the frame powers r2 (B,N,T):
+ * SSSPY_CONTRAST_LAPLACE 1 / floor(r), r = sqrt(r2) (the floor acts on r, not on 2 r as in
+ * ssspy_iva_weight); SSSPY_CONTRAST_GAUSS refreshes variance = r2 / F and gives 1 / variance (no
+ * floor, as in the reference); SSSPY_CONTRAST_GAUSS_FIXED gives 1 / variance of the variance as it
+ * stands.  The score is phi_nj y_inj.  Up to SSSPY_RT_MAX_SOURCES (16) sources.
+ * replaces: ssspy/bss/iva.py:2441-2451, :2610-2611, :2646-2651, :2745-2760, :2924-2935, :2969-2973. */
+int ssspy_iva_score_weight(const double *r2, double *weight, double *variance, int B, int N, int F,
+                           int T, int contrast, int floor_kind, double floor_eps, void *stream);
+
+/* One gradient step on the filters W (B,F,N,N), in place:
+ *   P_i[n,m] = mean_j phi(y)_inj conj(y_imj),  D = P - I (holonomic) or offdiag(P),
+ *   W <- W - step_size D W (natural != 0) or W <- W - step_size D W^-H (LU with partial pivoting; a
+ *   singular bin bumps info[0] -- the reference raises LinAlgError from np.linalg.inv).
+ * stats: the frame-weighted covariances U (B,F,N,N,N) of the mixture under the score weights
+ * (ssspy_weighted_covariance, SSSPY_WEIGHT_FRAME), row n of P being (W U_n W^H)[n,:]; or, with
+ * stats_ready != 0, P itself (B,F,N,N) (ssspy_cross_covariance of the scores and the estimate: user
+ * score functions).  logdet (may be NULL): the launch also leaves sum_i log|det W_i| of the filters
+ * it STARTS from, as ssspy_iva_grad_step_logdet_slots() shares per mixture at
+ * logdet[s * logdet_stride + b], to be added in slot order (ssspy_fold_scalar_slots); no atomics.
+ * 2..8 sources are compiled per source count (a bin on 2 / 4 / 8 lanes, registers only), 9..16 take
+ * the count at run time (correct, not tuned); SSSPY_ERR_UNSUPPORTED above 16.
+ * replaces: ssspy/bss/iva.py:797-818, :969-988 (and np.linalg.slogdet at :234 for the loss). */
+int ssspy_iva_grad_step_logdet_slots(int B, int F, int N);
+int ssspy_iva_grad_step(void *W, const void *stats, int stats_ready, int B, int F, int N,
+                        int natural, int holonomic, double step_size, int *info, double *logdet,
+                        long long logdet_stride, void *stream);
+
 /* ------------------------------------------------------------------ FastGaussMNMF (IP1) */
 
 /* steps of FastGaussMNMF.update_once, OR-ed into `steps` of ssspy_fastmnmf_update */

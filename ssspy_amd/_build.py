@@ -45,6 +45,7 @@ def _units():
         ("spatial_kernels.hip", "spatial_kernels.o", []),
         ("ilrma_api.hip", "ilrma_api.o", []),
         ("iva_kernels.hip", "iva_kernels.o", []),
+        ("grad_iva.hip", "grad_iva.o", []),
         ("iss_fused.hip", "iss_fused.o", []),
         ("linalg_kernels.hip", "linalg_kernels.o", []),
         ("pairwise_kernels.hip", "pairwise_kernels.o", []),

@@ -672,6 +672,41 @@ def iva_loss_data(r2, variance, n_bins, contrast, out=None):
     return out
 
 
+def iva_score_weight(r2, n_bins, contrast, flooring, weight=None, variance=None):
+    """Score weights of the gradient IVA classes: Laplace 1 / floor(r), Gauss 1 / alpha with the
+    variance alpha = r2 / n_bins refreshed in ``variance``; (B, N, T)."""
+    B, N, T = r2.shape
+    if weight is None:
+        weight = dv.empty((B, N, T), dv.f64, r2.device)
+    _lib.check(
+        _L().ssspy_iva_score_weight(ptr(r2), ptr(weight), ptr(variance), B, N, n_bins, T, contrast,
+                                    flooring[0], flooring[1], _st()),
+        "iva_score_weight",
+    )
+    return weight
+
+
+def iva_grad_step_logdet_slots(B, F, N):
+    """Shares per mixture ``iva_grad_step`` leaves in ``logdet``."""
+    return int(_L().ssspy_iva_grad_step_logdet_slots(B, F, N))
+
+
+def iva_grad_step(W, stats, natural, holonomic, step_size, info, logdet=None, logdet_stride=0):
+    """W <- W - step_size D W (natural) or D W^-H in place, D from ``stats``: the weighted covariances
+    (B, F, N, N, N) of the mixture, or mean_j phi(y) y^H (B, F, N, N) itself.  ``logdet``: shares of
+    sum_i log|det W_i| of the filters as they come in, at logdet[s * logdet_stride + b]."""
+    B, F, N, _ = W.shape
+    ready = stats.dim() == 4
+    assert tuple(stats.shape) == ((B, F, N, N) if ready else (B, F, N, N, N))
+    _lib.check(
+        _L().ssspy_iva_grad_step(ptr(W), ptr(stats), int(ready), B, F, N, int(bool(natural)),
+                                 int(bool(holonomic)), float(step_size), ptr(info), ptr(logdet),
+                                 int(logdet_stride), _st()),
+        "iva_grad_step",
+    )
+    return W
+
+
 # ----------------------------------------------------------------------------- FastMNMF
 def fastmnmf_workspace(B, N, M, F, T, K, dev):
     return _workspace(_L().ssspy_fastmnmf_workspace_bytes(B, N, M, F, T, K), dev)

@@ -1,16 +1,22 @@
-"""Auxiliary-function independent vector analysis (AuxIVA) on MI355X.
+"""Independent vector analysis (IVA) on MI355X: the auxiliary-function and the gradient families.
 
 Drop-in separator classes for the ``AuxIVA`` family of the reference's ``ssspy.bss.iva``
 (ssspy/bss/iva.py:553-641, :1403-2214, :2976-3473): ``AuxIVA``, ``AuxLaplaceIVA`` and
-``AuxGaussIVA`` with ``spatial_algorithm in {"IP", "IP1", "ISS", "ISS1"}``.  The contrast
+``AuxGaussIVA`` with every ``spatial_algorithm`` of the reference.  The contrast
 functions of the reference are Python closures; the kernels implement the two the
 reference ships (Laplace: G = 2r; time-varying Gauss: G = F log(alpha) + r^2/alpha).  A
 user-supplied ``d_contrast_fn`` is evaluated on the host on the (n_sources, n_frames) frame norms
 the device produces (a few KB per iteration; both passes over the spectrogram stay in the kernels);
 a user-supplied ``contrast_fn`` takes the whole estimate and is evaluated on a host copy of it,
 only when the loss is recorded.
-The gradient / natural-gradient / Fast / PDS / ADMM IVA variants are out of scope
-(SURVEY.md section 2, row 3).
+
+The gradient family (ssspy/bss/iva.py:284-406, :644-988, :2341-2973): ``GradIVA``,
+``NaturalGradIVA`` and the four classes with a built-in source model, ``GradLaplaceIVA``,
+``GradGaussIVA``, ``NaturalGradLaplaceIVA`` and ``NaturalGradGaussIVA``.  The score of the four is
+one real weight per (source, frame) times the estimate, so an iteration is the two read-only passes
+over the mixture of AuxIVA-IP1 and a per-bin step (csrc/grad_iva.hip); the two generic classes
+take Python closures on the whole estimate and run a compatibility path (see ``GradIVABase``).
+The Fast / Faster / PDS / ADMM IVA variants are out of scope.
 """
 
 import functools
@@ -27,7 +33,18 @@ from ._device_state import LossShares, Synced
 from ._filter_base import _IP1, _IP2, _IPA, _ISS1, _ISS2, DemixingFilterBase
 from .base import IterativeMethodBase
 
-__all__ = ["AuxIVA", "AuxLaplaceIVA", "AuxGaussIVA"]
+__all__ = [
+    "GradIVABase",
+    "GradIVA",
+    "NaturalGradIVA",
+    "AuxIVA",
+    "GradLaplaceIVA",
+    "GradGaussIVA",
+    "NaturalGradLaplaceIVA",
+    "NaturalGradGaussIVA",
+    "AuxLaplaceIVA",
+    "AuxGaussIVA",
+]
 
 spatial_algorithms = ["IP", "IP1", "IP2", "ISS", "ISS1", "ISS2", "IPA"]
 EPS = 1e-10
@@ -629,3 +646,453 @@ class AuxGaussIVA(AuxIVA):
         """ref: ssspy/bss/iva.py:3319-3337 (variance refresh) + :3339-3463 (pairs, fixed variance)."""
         self.update_source_model()
         super().update_once_ip2(flooring_fn=flooring_fn)
+
+
+# ------------------------------------------------------------------ gradient / natural gradient
+def _device_score(method):
+    """Which built-in source model the separator's pair of callables stands for, or None for user
+    closures.  The four named classes tag the closures they build with the model and with the
+    instance they belong to: closures borrowed from another instance read that instance's floor or
+    variance, so they count as user closures and take the compatibility path."""
+    tags = [(getattr(fn, "_ssspy_amd_contrast", None), getattr(fn, "_ssspy_amd_owner", None))
+            for fn in (method.contrast_fn, method.score_fn)]
+    if tags[0][0] is None or tags[0][0] != tags[1][0] or any(t[1] is not method for t in tags):
+        return None
+    return tags[0][0]
+
+
+class GradIVABase(IVABase):
+    """IVA by (natural) gradient descent (ref: ssspy/bss/iva.py:284-406).
+
+    With the source models of the four named subclasses the score is phi_nj y_inj with one real
+    weight per (source, frame), hence mean_j phi(y) y^H = W U_n W^H (row n) with the frame-weighted
+    covariances U_n of the mixture: an iteration is the frame-power pass, the covariance pass and one
+    per-bin step, all on the device, and ``output`` is formed when somebody reads it.
+
+    With user closures (``GradIVA`` / ``NaturalGradIVA`` constructed directly) this is the
+    compatibility path, not the fast one: ``score_fn`` takes the whole (n_sources, n_bins, n_frames)
+    estimate, so the estimate comes to the host once per iteration and the scores go back up;
+    mean_j phi(y) y^H is then the cross-covariance operator and the step kernel takes it as it is.
+    ``contrast_fn`` is evaluated on a host copy of the estimate, only when the loss is recorded.
+    """
+
+    _natural = False
+    variance = None  # (the Gauss classes keep one)
+
+    def __init__(
+        self,
+        step_size: float = 1e-1,
+        contrast_fn: Callable[[np.ndarray], np.ndarray] = None,
+        score_fn: Callable[[np.ndarray], np.ndarray] = None,
+        flooring_fn: Optional[Callable[[np.ndarray], np.ndarray]] = functools.partial(
+            max_flooring, eps=EPS
+        ),
+        callbacks: Optional[Union[Callable, List[Callable]]] = None,
+        is_holonomic: bool = False,
+        scale_restoration: Union[bool, str] = True,
+        record_loss: bool = True,
+        reference_id: int = 0,
+    ) -> None:
+        super().__init__(
+            flooring_fn=flooring_fn,
+            callbacks=callbacks,
+            scale_restoration=scale_restoration,
+            record_loss=record_loss,
+            reference_id=reference_id,
+        )
+        self.step_size = step_size
+        if contrast_fn is None:
+            raise ValueError("Specify contrast function.")
+        self.contrast_fn = contrast_fn
+        if score_fn is None:
+            raise ValueError("Specify score function.")
+        self.score_fn = score_fn
+        self.is_holonomic = is_holonomic
+
+    def __call__(
+        self, input: np.ndarray, n_iter: int = 100, initial_call: bool = True, **kwargs
+    ) -> np.ndarray:
+        """Separate a frequency-domain multichannel mixture (ref: ssspy/bss/iva.py:359-392)."""
+        self._bind_input(input)
+        self._reset(**kwargs)
+        if not self._iterate_with_resident_loss(int(n_iter), initial_call):
+            IterativeMethodBase.__call__(self, n_iter=n_iter, initial_call=initial_call)
+        return self._finish_call()
+
+    def __repr__(self) -> str:
+        s = "GradIVA(step_size={}, is_holonomic={}, scale_restoration={}, record_loss={}".format(
+            self.step_size, self.is_holonomic, self.scale_restoration, self.record_loss
+        )
+        if self.scale_restoration:
+            s += ", reference_id={}".format(self.reference_id)
+        return s + ")"
+
+    def _reset(self, **kwargs) -> None:
+        """ref: ssspy/bss/iva.py:138-169."""
+        assert self._has_input(), "Specify data!"
+        if self._X.shape[1] > _lib.RT_MAX_SOURCES:
+            raise NotImplementedError(
+                "{} takes up to {} sources, got {}.".format(
+                    type(self).__name__, _lib.RT_MAX_SOURCES, self._X.shape[1]))
+        super()._reset(**kwargs)
+        self._score = _device_score(self)
+
+    def _variance_tensor(self):
+        return None
+
+    def _fill_output(self) -> None:
+        ent = self._state()["output"]
+        if ent["dev"] is None:
+            ent["dev"] = dv.empty(tuple(self._X.shape), dv.c128, self._X.device)
+        _ops.separate(self._X, self._state_dev("demix_filter"), out=ent["dev"])
+
+    def _filters_stepped(self) -> None:
+        """Behind a step: the filters moved, ``output`` follows them when it is read
+        (the reference's ``self.output = Y`` at the end of update_once, ssspy/bss/iva.py:815-818)."""
+        self._state_touch("demix_filter")
+        self._state_defer("output", self._fill_output)
+        if self._variance_tensor() is not None:
+            self._state_touch("variance")
+
+    def _score_weights(self, r2, refresh=True):
+        """phi_nj (B, N, T) from the frame powers; the Gauss model refreshes its variance on the
+        way unless ``refresh`` is False (an overridden ``update_source_model`` has set it)."""
+        if self._score == _lib.CONTRAST_LAPLACE and host_floor(self._floor) is not None:
+            # a flooring callable the kernels cannot run: on the host, on the (n_sources, 1,
+            # n_frames) norms it sees in the reference (ssspy/bss/iva.py:2448-2451)
+            self._check_device_errors()
+            r = np.sqrt(dv.to_host(r2))  # (B, N, T)
+            weight = np.stack([
+                1.0 / np.asarray(self.flooring_fn(rb[:, np.newaxis, :]), dtype=np.float64)[:, 0, :]
+                for rb in r])
+            return dv.to_device(weight, dtype=np.float64, dev=r2.device)
+        floor = self._floor if host_floor(self._floor) is None else device_flooring(identity)
+        contrast = self._score
+        if contrast == _lib.CONTRAST_GAUSS and not refresh:
+            contrast = _lib.CONTRAST_GAUSS_FIXED
+        return _ops.iva_score_weight(r2, self.n_bins, contrast, floor,
+                                     variance=self._variance_tensor())
+
+    def _step(self, r2=None, logdet=None, logdet_stride=0, refresh=True) -> None:
+        """One update of the filters with a built-in source model, on the device."""
+        W = self._state_dev("demix_filter")
+        if r2 is None:
+            r2 = _ops.iva_frame_power(self._X, W)
+        weight = self._score_weights(r2, refresh)
+        U = _ops.weighted_covariance(self._X, weight, _lib.WEIGHT_FRAME, self.n_sources)
+        _ops.iva_grad_step(W, U, self._natural, self.is_holonomic, self.step_size,
+                           self._info_tensor(), logdet=logdet, logdet_stride=logdet_stride)
+
+    def update_once(self) -> None:
+        """ref: ssspy/bss/iva.py:764-818 (gradient), :936-988 (natural gradient)."""
+        if self._score is not None:
+            own = getattr(type(self), "update_source_model", None)
+            if own is not None and own is not _GradGaussMixin.update_source_model:
+                # a subclass's own source model, as the reference calls it before the step
+                # (ssspy/bss/iva.py:2640-2644); the step then takes the variance as it stands
+                self.update_source_model()
+                self._step(refresh=False)
+            else:
+                # (the stock refresh alpha = r^2 / n_bins runs inside the step's weight kernel)
+                self._step()
+        else:
+            W = self._state_dev("demix_filter")
+            Y = _ops.separate(self._X, W)
+            self._check_device_errors()
+            Phi = np.stack([np.asarray(self.score_fn(Yb), dtype=np.complex128)
+                            for Yb in dv.to_host(Y)])
+            if Phi.shape != tuple(Y.shape):
+                raise ValueError("score_fn must map (n_sources, n_bins, n_frames) to the same shape.")
+            PhiY = _ops.cross_covariance(dv.to_device(Phi, dtype=np.complex128, dev=Y.device), Y)
+            _ops.iva_grad_step(W, PhiY, self._natural, self.is_holonomic, self.step_size,
+                               self._info_tensor())
+        self._filters_stepped()
+
+    def compute_loss(self) -> float:
+        """ref: ssspy/bss/iva.py:200-222."""
+        W = self._state_dev("demix_filter")
+        logdet = _ops.sum_logdet(W)
+        if self._score is not None:
+            data = _ops.iva_loss_data(_ops.iva_frame_power(self._X, W), self._variance_tensor(),
+                                      self.n_bins, self._score)
+            return self._host_loss(data, logdet)
+        Y = dv.to_host(_ops.separate(self._X, W))
+        self._check_device_errors()
+        values = np.array([np.sum(np.mean(self.contrast_fn(Yb), axis=1), axis=0) for Yb in Y])
+        return self._loss_entry(values - 2.0 * dv.to_host(logdet))
+
+    def _iterate_with_resident_loss(self, n_iter: int, initial_call: bool) -> bool:
+        """``record_loss=True`` at the cost of ``record_loss=False`` when nothing can look at
+        ``self.loss`` in between (no callbacks, stock methods, a source model and a floor that run on
+        the device): the contrast term of the state after iteration t comes from the frame powers
+        iteration t + 1 forms anyway, sum_i log|det W_i| from the step kernel's shares, and the
+        terms stay in HBM until the end (_resident_loss).  The Gauss term is evaluated with the
+        variance as it stands BEFORE the step refreshes it: the reference's ``compute_loss`` sees the
+        variance of the start of the iteration against the new filters (ssspy/bss/iva.py:2625-2651).
+        False: the reference's loop."""
+        cls = type(self)
+        B, N = self._X.shape[0], self.n_sources
+        nld = _ops.iva_grad_step_logdet_slots(B, self.n_bins, N)
+        # (stock methods: the ones this module defines, the Gauss classes' own included)
+        methods = [getattr(cls, name, None) for name in (
+            "update_once", "compute_loss", "update_source_model", "_step", "_score_weights")]
+        stock = all(fn is None or fn.__module__ == __name__ for fn in methods)
+        if not (self._unobserved_loss(n_iter) and self._score is not None and stock
+                and host_floor(self._floor) is None and LossShares.fit(nld, n_iter + 1, B)):
+            return False
+
+        def prepare(data, logdet):
+            W = self._state_dev("demix_filter")
+            ld = LossShares(nld, n_iter + 1, B, self._X.device, logdet)
+
+            def step(t, record):
+                r2 = _ops.iva_frame_power(self._X, W)
+                if record:
+                    _ops.iva_loss_data(r2, self._variance_tensor(), self.n_bins, self._score,
+                                       out=data[t])
+                self._step(r2, ld.at(t), ld.stride)
+
+            def end():
+                _ops.iva_loss_data(_ops.iva_frame_power(self._X, W), self._variance_tensor(),
+                                   self.n_bins, self._score, out=data[n_iter])
+                ld.fold()
+                _ops.sum_logdet(W, out=logdet[n_iter])
+                self._filters_stepped()
+
+            return step, end
+        return self._resident_loss(n_iter, initial_call, prepare)
+
+
+class GradIVA(GradIVABase):
+    """IVA by gradient descent, W <- W - eta D W^-H (ref: ssspy/bss/iva.py:644-818).
+
+    With ``contrast_fn`` / ``score_fn`` closures this is the compatibility path of ``GradIVABase``."""
+
+    def __init__(
+        self,
+        step_size: float = 1e-1,
+        contrast_fn: Callable[[np.ndarray], np.ndarray] = None,
+        score_fn: Callable[[np.ndarray], np.ndarray] = None,
+        flooring_fn: Optional[Callable[[np.ndarray], np.ndarray]] = functools.partial(
+            max_flooring, eps=EPS
+        ),
+        callbacks: Optional[Union[Callable, List[Callable]]] = None,
+        is_holonomic: bool = True,
+        scale_restoration: Union[bool, str] = True,
+        record_loss: bool = True,
+        reference_id: int = 0,
+    ) -> None:
+        super().__init__(
+            step_size=step_size,
+            contrast_fn=contrast_fn,
+            score_fn=score_fn,
+            flooring_fn=flooring_fn,
+            callbacks=callbacks,
+            is_holonomic=is_holonomic,
+            scale_restoration=scale_restoration,
+            record_loss=record_loss,
+            reference_id=reference_id,
+        )
+
+
+class NaturalGradIVA(GradIVABase):
+    """IVA by natural gradient descent, W <- W - eta D W (ref: ssspy/bss/iva.py:821-988).
+
+    With ``contrast_fn`` / ``score_fn`` closures this is the compatibility path of ``GradIVABase``."""
+
+    _natural = True
+
+    def __init__(
+        self,
+        step_size: float = 1e-1,
+        contrast_fn: Callable[[np.ndarray], np.ndarray] = None,
+        score_fn: Callable[[np.ndarray], np.ndarray] = None,
+        flooring_fn: Optional[Callable[[np.ndarray], np.ndarray]] = functools.partial(
+            max_flooring, eps=EPS
+        ),
+        callbacks: Optional[Union[Callable, List[Callable]]] = None,
+        is_holonomic: bool = True,
+        scale_restoration: Union[bool, str] = True,
+        record_loss: bool = True,
+        reference_id: int = 0,
+    ) -> None:
+        super().__init__(
+            step_size=step_size,
+            contrast_fn=contrast_fn,
+            score_fn=score_fn,
+            flooring_fn=flooring_fn,
+            callbacks=callbacks,
+            is_holonomic=is_holonomic,
+            scale_restoration=scale_restoration,
+            record_loss=record_loss,
+            reference_id=reference_id,
+        )
+
+
+def _laplace_closures(method):
+    """The spherical Laplace model: G = 2 ||y||_2, phi = y / floor(||y||_2)
+    (ref: ssspy/bss/iva.py:2429-2451, :2733-2760)."""
+    def contrast_fn(y: np.ndarray) -> np.ndarray:
+        return 2 * np.linalg.norm(y, axis=1)
+
+    def score_fn(y: np.ndarray) -> np.ndarray:
+        norm = np.linalg.norm(y, axis=1, keepdims=True)
+        return y / method.flooring_fn(norm)
+
+    contrast_fn._ssspy_amd_contrast = score_fn._ssspy_amd_contrast = _lib.CONTRAST_LAPLACE
+    contrast_fn._ssspy_amd_owner = score_fn._ssspy_amd_owner = method
+    return contrast_fn, score_fn
+
+
+def _gauss_closures(method):
+    """The time-varying Gauss model: G = n_bins log(alpha) + ||y||^2 / alpha, phi = y / alpha
+    (ref: ssspy/bss/iva.py:2586-2611, :2908-2935)."""
+    def contrast_fn(y: np.ndarray) -> np.ndarray:
+        alpha = method.variance
+        norm = np.linalg.norm(y, axis=1)
+        return method.n_bins * np.log(alpha) + (norm**2) / alpha
+
+    def score_fn(y: np.ndarray) -> np.ndarray:
+        return y / method.variance[:, np.newaxis, :]
+
+    contrast_fn._ssspy_amd_contrast = score_fn._ssspy_amd_contrast = _lib.CONTRAST_GAUSS
+    contrast_fn._ssspy_amd_owner = score_fn._ssspy_amd_owner = method
+    return contrast_fn, score_fn
+
+
+class _GradGaussMixin:
+    """Variance state of the two Gauss classes (ref: ssspy/bss/iva.py:2613-2651, :2937-2973)."""
+
+    variance = Synced(dv.f64)
+
+    def _reset(self, **kwargs) -> None:
+        super()._reset(**kwargs)
+        self.variance = np.ones(self._lead() + (self.n_sources, self.n_frames))
+
+    def _variance_tensor(self):
+        return self._state_dev("variance")
+
+    def update_source_model(self) -> None:
+        """alpha_nj = mean_i |y_nij|^2 (ref: ssspy/bss/iva.py:2646-2651)."""
+        r2 = _ops.iva_frame_power(self._X, self._state_dev("demix_filter"))
+        _ops.iva_score_weight(r2, self.n_bins, _lib.CONTRAST_GAUSS, device_flooring(identity),
+                              variance=self._variance_tensor())
+        self._state_touch("variance")
+
+
+class GradLaplaceIVA(GradIVA):
+    """Gradient IVA with the spherical Laplace source model (ref: ssspy/bss/iva.py:2341-2501)."""
+
+    def __init__(
+        self,
+        step_size: float = 1e-1,
+        flooring_fn: Optional[Callable[[np.ndarray], np.ndarray]] = functools.partial(
+            max_flooring, eps=EPS
+        ),
+        callbacks: Optional[Union[Callable, List[Callable]]] = None,
+        is_holonomic: bool = True,
+        scale_restoration: Union[bool, str] = True,
+        record_loss: bool = True,
+        reference_id: int = 0,
+    ) -> None:
+        contrast_fn, score_fn = _laplace_closures(self)
+        super().__init__(
+            step_size=step_size,
+            contrast_fn=contrast_fn,
+            score_fn=score_fn,
+            flooring_fn=flooring_fn,
+            callbacks=callbacks,
+            is_holonomic=is_holonomic,
+            scale_restoration=scale_restoration,
+            record_loss=record_loss,
+            reference_id=reference_id,
+        )
+
+
+class GradGaussIVA(_GradGaussMixin, GradIVA):
+    """Gradient IVA with the time-varying Gauss source model (ref: ssspy/bss/iva.py:2504-2651)."""
+
+    def __init__(
+        self,
+        step_size: float = 1e-1,
+        flooring_fn: Optional[Callable[[np.ndarray], np.ndarray]] = functools.partial(
+            max_flooring, eps=EPS
+        ),
+        callbacks: Optional[Union[Callable, List[Callable]]] = None,
+        is_holonomic: bool = True,
+        scale_restoration: Union[bool, str] = True,
+        record_loss: bool = True,
+        reference_id: int = 0,
+    ) -> None:
+        contrast_fn, score_fn = _gauss_closures(self)
+        super().__init__(
+            step_size=step_size,
+            contrast_fn=contrast_fn,
+            score_fn=score_fn,
+            flooring_fn=flooring_fn,
+            callbacks=callbacks,
+            is_holonomic=is_holonomic,
+            scale_restoration=scale_restoration,
+            record_loss=record_loss,
+            reference_id=reference_id,
+        )
+
+
+class NaturalGradLaplaceIVA(NaturalGradIVA):
+    """Natural-gradient IVA with the spherical Laplace source model
+    (ref: ssspy/bss/iva.py:2654-2820)."""
+
+    def __init__(
+        self,
+        step_size: float = 1e-1,
+        flooring_fn: Optional[Callable[[np.ndarray], np.ndarray]] = functools.partial(
+            max_flooring, eps=EPS
+        ),
+        callbacks: Optional[Union[Callable, List[Callable]]] = None,
+        is_holonomic: bool = True,
+        scale_restoration: Union[bool, str] = True,
+        record_loss: bool = True,
+        reference_id: int = 0,
+    ) -> None:
+        contrast_fn, score_fn = _laplace_closures(self)
+        super().__init__(
+            step_size=step_size,
+            contrast_fn=contrast_fn,
+            score_fn=score_fn,
+            flooring_fn=flooring_fn,
+            callbacks=callbacks,
+            is_holonomic=is_holonomic,
+            scale_restoration=scale_restoration,
+            record_loss=record_loss,
+            reference_id=reference_id,
+        )
+
+
+class NaturalGradGaussIVA(_GradGaussMixin, NaturalGradIVA):
+    """Natural-gradient IVA with the time-varying Gauss source model
+    (ref: ssspy/bss/iva.py:2823-2973)."""
+
+    def __init__(
+        self,
+        step_size: float = 1e-1,
+        flooring_fn: Optional[Callable[[np.ndarray], np.ndarray]] = functools.partial(
+            max_flooring, eps=EPS
+        ),
+        callbacks: Optional[Union[Callable, List[Callable]]] = None,
+        is_holonomic: bool = True,
+        scale_restoration: Union[bool, str] = True,
+        record_loss: bool = True,
+        reference_id: int = 0,
+    ) -> None:
+        contrast_fn, score_fn = _gauss_closures(self)
+        super().__init__(
+            step_size=step_size,
+            contrast_fn=contrast_fn,
+            score_fn=score_fn,
+            flooring_fn=flooring_fn,
+            callbacks=callbacks,
+            is_holonomic=is_holonomic,
+            scale_restoration=scale_restoration,
+            record_loss=record_loss,
+            reference_id=reference_id,
+        )
