@@ -31,9 +31,9 @@ DECL_N(2) DECL_N(3) DECL_N(4) DECL_N(5) DECL_N(6) DECL_N(7) DECL_N(8)
                             double *, void *, int, hipStream_t, long long);                     \
   int ilrma_fast_basis_loss_slots_n##n(int, int, int);                                          \
   size_t ilrma_fast_loss_ws_bytes_n##n(int, int);                                               \
-  int ilrma_fast_activation_n##n(const void *, const void *, const double *, const double *,   \
+  int ilrma_fast_activation_n##n(const void *, const void *, const double *, double *,         \
                                  double *, int, int, int, int, int, int, double, int,           \
-                                 hipStream_t);                                                  \
+                                 hipStream_t, int *, int, int, double);                         \
   int ilrma_fast_wcov_n##n(const void *, const void *, const double *, const double *, void *, \
                            int, int, int, int, void *, int, double, int, double, hipStream_t,  \
                            int *, int *);                                                      \
@@ -892,6 +892,17 @@ static int update_activation_impl(const void *X, const void *W, const double *ba
   // (the partial sums of a run keep the (group, chunk, source) layout at the run's offset: every
   // source owns `chunks` slabs of 2 K T doubles wherever its group starts)
   const size_t part_per_source = (size_t)chunks * 2 * K * T;
+  // One chunk on the tuned kernels at n_basis <= 16: every work item holds the complete sums of its
+  // frames and can apply the update itself (k_activation_fast): no record of partial sums, no
+  // finalize launch; the launcher says whether it did.  The wider k ranges and the grouped runs of a
+  // wide mixture keep the fold.
+  // (-DSSSPY_NO_ACT_INPLACE: the record and the fold throughout, for A / B runs)
+#ifdef SSSPY_NO_ACT_INPLACE
+  const bool offer = false;
+#else
+  const bool offer = !nruns && chunks == 1 && K <= 16 && fast_path(N, F, T, K, domain, source_model);
+#endif
+  int finished = 0;
   auto run = [&]() -> int {
     if (nruns) {
       const char *Y = (const char *)X;
@@ -909,7 +920,8 @@ static int update_activation_impl(const void *X, const void *W, const double *ba
           ILRMA_FAST_DISPATCH(sr.G, ilrma_fast_activation, Y + (size_t)sr.first * F * T * elem,
                               nullptr, basis + sr.first * F * K, activation + sr.first * K * T,
                               part + sr.first * part_per_source, chunks, sr.count, F, T, K,
-                              fast_model_id(domain, source_model), fast_model_param(domain, source_model, model_param), power ? 1 : 0, st);
+                              fast_model_id(domain, source_model), fast_model_param(domain, source_model, model_param), power ? 1 : 0, st,
+                              nullptr, 0, 0, 0.0);
         };
         const int r = one();
         if (r) return r;
@@ -918,12 +930,13 @@ static int update_activation_impl(const void *X, const void *W, const double *ba
     }
     if (fast_path(N, F, T, K, domain, source_model)) {
       ILRMA_FAST_DISPATCH(N, ilrma_fast_activation, X, W, basis, activation, part, chunks, B, F, T,
-                          K, fast_model_id(domain, source_model), fast_model_param(domain, source_model, model_param), 0, st);
+                          K, fast_model_id(domain, source_model), fast_model_param(domain, source_model, model_param), 0, st,
+                          offer ? &finished : nullptr, d.me, floor_kind, floor_eps);
     }
     ILRMA_DISPATCH(N, ilrma_activation, X, W, basis, activation, part, chunks, d, st);
   };
   rc = run();
-  if (rc) return rc;
+  if (rc || finished) return rc;
   // fold the chunks in the layout the kernel wrote: (mixture, chunk, source) of the regrouped batch
   // when the wide-mixture path ran
   if (!nruns) {

@@ -73,6 +73,37 @@ typedef fast::XTile<N> XTile;
 // power |y|^2 as (B, N, F, T) f64 (the grouped passes of a wide mixture: half the bytes).
 enum { IN_Y = 0, IN_X = 1, IN_P = 2 };
 
+// Idle waves of an edge item.  F is n_fft / 2 + 1, so the last bin group of every mixture holds one
+// bin: three of the four 16-bin tiles of that basis item (one of the two of the covariance item) lie
+// wholly beyond F.  Their waves used to run the whole walk on clamped addresses and mask the result
+// away; now they only keep the workgroup in step: the same cooperative activation-tile staging and
+// the same number of barriers as the working waves, no x fetch, no demixing or basis operands, no
+// GEMM, no reciprocal, no store.  The working waves' instruction stream is untouched, so every
+// output bit is.  -DSSSPY_NO_IDLE_SKIP builds the old form (A / B runs).
+__device__ __forceinline__ bool wave_idle(int i0, int F) {
+#ifdef SSSPY_NO_IDLE_SKIP
+  return false;
+#else
+  return __builtin_amdgcn_readfirstlane(i0) >= F;  // i0 is wave-uniform: a scalar branch
+#endif
+}
+
+// the bin-major walk of an idle wave (basis and loss passes): its share of the staged activation
+// tiles, barrier for barrier what the working waves do
+template <int KR, bool FULL>
+__device__ __forceinline__ void idle_wave_walk(double (&vs)[2][N * KR * VROW], const double *act_b,
+                                               int K, int T, int jt_begin, int jt_end, int ntiles) {
+  fast::VStage<N, KR> st;
+  fast::vstage_load<N, KR, FULL>(st, act_b, K, T, min(jt_begin, ntiles - 1) * 16);
+  fast::vstage_store<N, KR>(st, vs[0]);
+  __syncthreads();
+  for (int jt = jt_begin; jt < jt_end; ++jt) {
+    fast::vstage_load<N, KR, FULL>(st, act_b, K, T, min(jt + 1, jt_end - 1) * 16);
+    fast::vstage_store<N, KR>(st, vs[(jt - jt_begin + 1) & 1]);
+    __syncthreads();
+  }
+}
+
 #if SSSPY_FAST_PART != 2
 // =============================================================================== basis (pass 1)
 // grid: (ceil(F/64), 1, B); 256 threads; wave w owns bins [64*bx + 16w, +16).
@@ -153,6 +184,20 @@ __global__ __launch_bounds__(256, KS >= 8 ? 1 : 2) void k_basis_fast(const c128 
       PIN ? fast::make_psrc<N>(reinterpret_cast<const double *>(X) + (long long)b * N * F * T, F, T)
           : fast::make_xsrc<N>(X + (long long)b * N * F * T, F, T);
   const double *act_b = act + (long long)b * N * K * T;
+  const int ntiles = (T + 15) >> 4;
+  const int tpc = (ntiles + nchunks - 1) / nchunks;
+  const int jt_begin = work.chunk * tpc, jt_end = min(ntiles, jt_begin + tpc);
+  // (the GGD instance with the loss by-product at 4 sources already spills 107 VGPRs and the extra
+  //  exit costs it 45 more: it keeps the old form)
+  constexpr bool SKIP_IDLE = !(N == 4 && MODEL == FM_GGD && LOSS);
+  if (SKIP_IDLE && wave_idle(i0, F)) {
+    idle_wave_walk<KR, FULL>(vs, act_b, K, T, jt_begin, jt_end, ntiles);
+    if (LOSS && lane == 0) {  // the fold adds every slot: an empty tile's share is +0.0
+      const int maxsplit = plan.split > 1 ? plan.split : 1;
+      loss_slots[(long long)((work.group * maxsplit + work.chunk) * 4 + wave) * B + b] = 0.0;
+    }
+    return;
+  }
 
   // demixing matrices of the wave's 16 bins -> LDS (wave-private region, filled by the wave)
   for (int e = lane; e < 16 * N * N; e += 64) {
@@ -183,9 +228,6 @@ __global__ __launch_bounds__(256, KS >= 8 ? 1 : 2) void k_basis_fast(const c128 
       den[n][ti] = double4_t{0.0, 0.0, 0.0, 0.0};
     }
 
-  const int ntiles = (T + 15) >> 4;
-  const int tpc = (ntiles + nchunks - 1) / nchunks;
-  const int jt_begin = work.chunk * tpc, jt_end = min(ntiles, jt_begin + tpc);
   fast::VStage<N, KR> st;
   XTile cur;
   fast::PTile<N> pcur;
@@ -411,6 +453,16 @@ __global__ __launch_bounds__(256, 2) void k_loss_fast(const c128 *__restrict__ X
   const int bin = min(i0 + c, F - 1);
   const fast::XSrc<N> xsrc = fast::make_xsrc<N>(X + (long long)b * N * F * T, F, T);
   const double *act_b = act + (long long)b * N * K * T;
+  const int ntiles = (T + 15) >> 4;
+  const int tpc = (ntiles + nchunks - 1) / nchunks;
+  const int jt_begin = work.chunk * tpc, jt_end = min(ntiles, jt_begin + tpc);
+  if (wave_idle(i0, F)) {  // see wave_idle(): in step with the others, and +0.0 for its slot
+    idle_wave_walk<16, false>(vs, act_b, K, T, jt_begin, jt_end, ntiles);
+    const int maxsplit = plan.split > 1 ? plan.split : 1;
+    if (lane == 0)
+      slots[(long long)((work.group * maxsplit + work.chunk) * 4 + wave) * B + b] = 0.0;
+    return;
+  }
   for (int e = lane; e < 16 * N * N; e += 64) {
     const int bl = e / (N * N), rem = e % (N * N);
     const int bi = min(i0 + bl, F - 1);
@@ -426,9 +478,6 @@ __global__ __launch_bounds__(256, 2) void k_loss_fast(const c128 *__restrict__ X
       const int kk = 4 * ks + q;
       tb[n][ks] = kk < K ? basis[(((long long)b * N + n) * F + bin) * K + kk] : 0.0;
     }
-  const int ntiles = (T + 15) >> 4;
-  const int tpc = (ntiles + nchunks - 1) / nchunks;
-  const int jt_begin = work.chunk * tpc, jt_end = min(ntiles, jt_begin + tpc);
   VStage st;
   XTile cur;
   fast::vstage_load<N>(st, act_b, K, T, min(jt_begin, ntiles - 1) * 16);
@@ -632,6 +681,22 @@ __global__ __launch_bounds__(256, KS >= 16 ? 1 : 2) void k_wcov_fast(const c128 
   const fast::XSrc<N> xsrc = fast::make_xsrc<N>(X + (long long)b * N * F * T, F, T);
   c128 *xshare = &xpatch[0][0] + wb * (N * 16 * 17);  // WC_SHARE: one patch per bin tile
   const double *act_b = act + (long long)b * N * K * T;
+  const int ntiles = (T + 15) >> 4;
+  const int tpc = (ntiles + nchunks - 1) / nchunks;
+  const int jt_begin = work.chunk * tpc, jt_end = min(ntiles, jt_begin + tpc);
+  if (wave_idle(i0, F)) {
+    // an empty bin tile (see wave_idle(); both of its waves): nothing to fetch or store, only the
+    // barriers of the walk -- the one behind the demixing rows and the two of every shared tile
+    // (the private-tile forms of 2 and 3 sources have none)
+    if (NEEDS_Y) __syncthreads();
+    if constexpr (WC_SHARE) {
+      for (int jt = jt_begin; jt < jt_end; ++jt) {
+        __syncthreads();
+        __syncthreads();
+      }
+    }
+    return;
+  }
   double tb[SG][KS];
 #pragma unroll
   for (int s = 0; s < SG; ++s)
@@ -659,9 +724,6 @@ __global__ __launch_bounds__(256, KS >= 16 ? 1 : 2) void k_wcov_fast(const c128 
   }
   double *phi_tile = phis + (SPLIT ? wb * (N * 4 * 64) : 0);
   const int gu = __builtin_amdgcn_readfirstlane(g);
-  const int ntiles = (T + 15) >> 4;
-  const int tpc = (ntiles + nchunks - 1) / nchunks;
-  const int jt_begin = work.chunk * tpc, jt_end = min(ntiles, jt_begin + tpc);
   XTile cur;
   if (NEEDS_Y) __syncthreads();
   for (int jt = jt_begin; jt < jt_end; ++jt) {
@@ -832,9 +894,18 @@ __global__ __launch_bounds__(256, 2) void k_wcov_frame_fast(const c128 *__restri
   const fast::XSrc<N> xsrc = fast::make_xsrc<N>(Xb, F, T);
   c128 *xshare = &xpatch[0][0] + wb * (N * 16 * 17);  // WC_SHARE: one patch per bin tile
   const double *wgt = weight + (long long)b * N * T;
+  const int ntiles = (T + 15) >> 4;
+  if (wave_idle(i0, F)) {  // an empty bin tile: the two barriers of every shared tile, nothing else
+    if constexpr (WC_SHARE) {
+      for (int jt = 0; jt < ntiles; ++jt) {
+        __syncthreads();
+        __syncthreads();
+      }
+    }
+    return;
+  }
   CovAcc<N, SG> acc;
   acc.clear();
-  const int ntiles = (T + 15) >> 4;
   XTile cur;
   for (int jt = 0; jt < ntiles; ++jt) {
     const int j0 = jt * 16;
@@ -963,11 +1034,22 @@ __device__ __forceinline__ void tstage_store(const TStage<KS> &st, double *tbuf,
 // KS = 8 / 16 (16 < n_basis <= 32 / 64): grid.y carries (bin chunk, k tile); every k-tile item runs
 // GEMM1 over all k and keeps the sums of its own 16 (see k_basis_fast); one wave per SIMD.
 // FULL: K == 4 KS (launcher-checked): no k masks (see k_basis_fast)
-template <int IN, int MODEL, int KS, bool FULL = false>
+// FIN (n_basis <= 16 and one chunk, launcher-checked): the sums of the item are complete, and the
+// workgroup is the only reader (the GEMM1 operand below) and the only writer of the activation
+// columns of its 64 frames, so the epilogue applies the update in place, the way k_basis_fast
+// finishes its unsplit items: no record, no k_ilrma_activation_finalize.  Same expression as that
+// kernel (ilrma_api.hip), term by term, so the result is the same bit for bit.  `act` is read and
+// written: no __restrict__.  An instance of its own, so that the record form keeps its registers
+// (as a run-time switch the extra live arguments cost the GGD and domain-p instances 2-6 more
+// spilled VGPRs).  Not built for the wider k ranges: at 16 < n_basis <= 32 and 2 sources the
+// epilogue takes the kernel from two waves per SIMD to one, above 32 the k tiles of a frame group
+// are separate items that read each other's rows.
+template <int IN, int MODEL, int KS, bool FULL = false, bool FIN = false>
 __global__ __launch_bounds__(256, KS >= 8 ? 1 : 2) void k_activation_fast(
     const c128 *__restrict__ X, const c128 *__restrict__ W, const double *__restrict__ basis,
-    const double *__restrict__ act, double *__restrict__ part, int F, int T, int K,
-    int tiles_per_chunk, int nchunks, FastModel fm) {
+    double *act, double *__restrict__ part, int F, int T, int K, int tiles_per_chunk, int nchunks,
+    FastModel fm, int me, int floor_kind, double eps) {
+  static_assert(!FIN || KS == 4, "in-place finish: one k tile");
   constexpr bool HAS_W = IN == IN_X, PIN = IN == IN_P;
   constexpr int TROW = trow<KS>();
   __shared__ __attribute__((aligned(16))) double ts[2][N * 16 * TROW];
@@ -1076,6 +1158,18 @@ __global__ __launch_bounds__(256, KS >= 8 ? 1 : 2) void k_activation_fast(
       for (int r = 0; r < 4; ++r) {
         const int ok = 16 * (kt0 + ti) + q + 4 * r;
         if (ok < K && fvalid) {
+          if constexpr (FIN) {
+            // the old value is the GEMM1 operand of k-step r: k = 4 r + q
+            const double told = vb[n][r];
+            // sums start from 0.0 + x as the fold's do (signed zeros); the power as mm_ratio_pow()
+            const double sn = 0.0 + numv[n][ti][r], sd = 0.0 + denv[n][ti][r];
+            const double ratio = sn / sd;
+            const double rp = me ? ratio
+                                 : ((MODEL == FM_GAUSS || MODEL == FM_T) ? sqrt(ratio)
+                                                                         : pow(ratio, fm.expo));
+            act[(((long long)b * N + n) * K + ok) * T + jf] = apply_floor(rp * told, floor_kind, eps);
+            continue;
+          }
           const long long base = ((((long long)b * nchunks + chunk) * N + n) * 2) * K;
           part[(base + ok) * T + jf] = numv[n][ti][r];
           part[(base + K + ok) * T + jf] = denv[n][ti][r];
@@ -1251,10 +1345,14 @@ size_t LAUNCHER(ilrma_fast_loss_ws_bytes)(int B, int F) {
 #endif
 
 #if SSSPY_FAST_PART != 1
-int LAUNCHER(ilrma_fast_activation)(const void *X, const void *W, const double *basis,
-                                    const double *act, double *part, int nchunks, int B, int F,
-                                    int T, int K, int fmodel, double mparam, int power_in,
-                                    hipStream_t st) {
+// finished != nullptr: the caller offers the in-place finish (see k_activation_fast; it needs
+// nchunks == 1 and K <= 16, and gives the exponent switch `me` and the floor).  *finished = 1: the
+// pass has applied the update to `act` and written no record.  Otherwise `act` is only read and the
+// sums go to `part` for k_ilrma_activation_finalize.
+int LAUNCHER(ilrma_fast_activation)(const void *X, const void *W, const double *basis, double *act,
+                                    double *part, int nchunks, int B, int F, int T, int K,
+                                    int fmodel, double mparam, int power_in, hipStream_t st,
+                                    int *finished, int me, int floor_kind, double floor_eps) {
   if (power_in && W != nullptr)
     return fail(SSSPY_ERR_BADARG, "ilrma_fast_activation: power input excludes a filter");
   const int ntiles = (F + 15) / 16;
@@ -1266,10 +1364,29 @@ int LAUNCHER(ilrma_fast_activation)(const void *X, const void *W, const double *
 #else
   const int item_tiles = ktiles == 2 ? 1 : ktiles;  // n_basis <= 32: both k tiles inside the item
 #endif
+  if (finished && (nchunks != 1 || ktiles != 1 || power_in))
+    return fail(SSSPY_ERR_BADARG, "ilrma_fast_activation: in-place finish needs one chunk and n_basis <= 16");
+  // (4 sources with a filter, GGD and domain-p models: the in-place instances spill 2 and 9 VGPRs
+  //  more than the record ones, which already spill 22 and 30: they keep the record and the fold)
+  const bool finish = finished != nullptr &&
+                      !(N == 4 && W != nullptr && (fmodel == FM_GGD || fmodel == FM_GAUSSP));
+  if (finished) *finished = finish ? 1 : 0;
   dim3 grid((T + 63) / 64, nchunks * item_tiles, B), block(256);
-#define SSSPY_ACT_LAUNCH_F(HW, M, KS_, FULL_)                                                    \
-  hipLaunchKernelGGL((k_activation_fast<HW, M, KS_, FULL_>), grid, block, 0, st, (const c128 *)X, \
-                     (const c128 *)W, basis, act, part, F, T, K, tiles_per_chunk, nchunks, fm)
+#define SSSPY_ACT_LAUNCH_K(HW, M, KS_, FULL_, FIN_)                                              \
+  hipLaunchKernelGGL((k_activation_fast<HW, M, KS_, FULL_, FIN_>), grid, block, 0, st,            \
+                     (const c128 *)X, (const c128 *)W, basis, act, part, F, T, K, tiles_per_chunk, \
+                     nchunks, fm, me, floor_kind, floor_eps)
+  // (KS_ == 4 && finish: the in-place instance; the power input never asks for it)
+#define SSSPY_ACT_LAUNCH_F(HW, M, KS_, FULL_)                          \
+  do {                                                                 \
+    if (KS_ == 4 && HW != IN_P && finish) {                            \
+      /* (where `finish` is never set, see above, the in-place instance is not launched) */ \
+      SSSPY_ACT_LAUNCH_K((HW != IN_P ? HW : IN_X), M, 4, FULL_,                       \
+                         (!(N == 4 && HW == IN_X && (M == FM_GGD || M == FM_GAUSSP)))); \
+      break;                                                           \
+    }                                                                  \
+    SSSPY_ACT_LAUNCH_K(HW, M, KS_, FULL_, false);                      \
+  } while (0)
 #define SSSPY_ACT_LAUNCH(HW, M, KS_) SSSPY_ACT_LAUNCH_F(HW, M, KS_, false)
 #define SSSPY_ACT_LAUNCH_M(HW, KS_)                        \
   switch (fmodel) {                                        \
@@ -1309,6 +1426,7 @@ int LAUNCHER(ilrma_fast_activation)(const void *X, const void *W, const double *
 #undef SSSPY_ACT_LAUNCH_M
 #undef SSSPY_ACT_LAUNCH
 #undef SSSPY_ACT_LAUNCH_F
+#undef SSSPY_ACT_LAUNCH_K
   return check_launch("k_activation_fast");
 }
 
