@@ -466,6 +466,35 @@ size_t ssspy_fold_scalar_slots_workspace_bytes(long long total, int nslots);
 int ssspy_fold_scalar_slots(const double *slots, long long total, int nslots, double *out,
                             void *workspace, size_t workspace_bytes, void *stream);
 
+/* Which kernels the ILRMA passes above take for a shape and model (host only, launches nothing): for
+ * tests and tools that must know which launcher branch a case exercises.  The value names the route
+ * of the basis / activation updates, first match in this order:
+ *   RUNTIME_N   more than SSSPY_MAX_SOURCES sources: covariance, IP1, normalisation and loss take the
+ *               source count at run time (wide_n.hip); the NMF passes walk the sources in groups of
+ *               the tuned kernels where the model has them, else as dense products
+ *   GROUPED     5..8 sources on the tuned kernels in runs of 4 / 3 / 2 sources
+ *   LATENCY     a handful of mixtures of 2..4 sources, n_basis <= 16 (ilrma_small.hip)
+ *   WIDE_BASIS  dense products on the matrix cores (wide_basis.hip): n_basis >= 33
+ *   THROUGHPUT  the tuned kernels of 2..4 sources (ilrma_fast.hip), n_basis <= 32
+ *   GENERIC     the per-source-count kernels of any model (ilrma_kernels.hip)
+ * (the basis update has no latency form: LATENCY shapes run the THROUGHPUT basis kernel.)
+ * *act_chunks (may be NULL): the number of bin chunks the activation pass of the THROUGHPUT, GROUPED
+ * and GENERIC routes folds (1: no partial sums).
+ * basis_plan (may be NULL): three ints on the frame splits of the basis pass on the LATENCY and
+ * THROUGHPUT routes -- work items (bin groups of 64 bins) that walk all frames and finish in place,
+ * items whose frames are split, and the number of frame chunks of a split item (1: none is split;
+ * 0, 0, 1 on the other routes).  Returns -1 for arguments the passes reject. */
+enum {
+  SSSPY_ROUTE_LATENCY = 0,
+  SSSPY_ROUTE_THROUGHPUT = 1,
+  SSSPY_ROUTE_GROUPED = 2,
+  SSSPY_ROUTE_GENERIC = 3,
+  SSSPY_ROUTE_WIDE_BASIS = 4,
+  SSSPY_ROUTE_RUNTIME_N = 5,
+};
+int ssspy_ilrma_route(int B, int N, int F, int T, int K, double domain, int source_model,
+                      int *act_chunks, int *basis_plan);
+
 /* IPA (iterative projection with adjustment): a whole sweep on per-bin statistics (round 5; the
  * per-source entry point ssspy_ipa_transform of rounds 3-5 went in round 6 with its 81 kernel
  * instantiations).  n_sources in [2, 16]: a lane per bin up to 6 sources, a bin on 8 lanes at 7 / 8,

@@ -20,6 +20,9 @@ SOURCE_GAUSS, SOURCE_T, SOURCE_GGD = 0, 1, 2
 PARTITION_LATENT, PARTITION_BASIS, PARTITION_ACTIVATION = 1, 2, 4
 SOURCE_ME = 0x100  # OR-ed into the model: source_algorithm="ME"
 CONTRAST_LAPLACE, CONTRAST_GAUSS, CONTRAST_GAUSS_FIXED = 0, 1, 2
+# SSSPY_ROUTE_*: what ssspy_ilrma_route returns
+(ROUTE_LATENCY, ROUTE_THROUGHPUT, ROUTE_GROUPED, ROUTE_GENERIC, ROUTE_WIDE_BASIS,
+ ROUTE_RUNTIME_N) = range(6)
 MAX_PAIRS = 32
 # SSSPY_MAX_SOURCES (per-N kernels: IPA, both MNMF classes, the Hermitian operators; GaussMNMF's
 # channels and the ILRMA partition entry points stop there), SSSPY_RT_MAX_SOURCES (run-time-N kernels:
@@ -98,6 +101,8 @@ PROTOTYPES = {
                                                _d, _i, _i, _d, _p, _z, _p, _p, _q, _p, _p]),
     "ssspy_fold_scalar_slots_workspace_bytes": (_z, [_q, _i]),
     "ssspy_fold_scalar_slots": (_i, [_p, _q, _i, _p, _p, _z, _p]),
+    "ssspy_ilrma_route": (_i, [_i, _i, _i, _i, _i, _d, _i, ctypes.POINTER(ctypes.c_int),
+                                ctypes.POINTER(ctypes.c_int)]),
     "ssspy_ilrma_partition_expand": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "ssspy_ilrma_partition_update": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _d, _i, _d,
                                           _i, _i, _d, _p, _z, _p]),

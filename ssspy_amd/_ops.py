@@ -589,6 +589,21 @@ def fold_scalar_slots(slots, total, nslots, out):
     return out
 
 
+def ilrma_route(B, N, F, T, K, domain, model=GAUSS):
+    """(route, act_chunks, basis_plan): the _lib.ROUTE_* the ILRMA passes take for this shape and
+    model, the number of bin chunks the activation pass folds, and the basis pass's (unsplit items,
+    split items, frame chunks per split item).  Host only."""
+    import ctypes
+
+    chunks = ctypes.c_int(0)
+    plan = (ctypes.c_int * 3)()
+    route = int(_L().ssspy_ilrma_route(B, N, F, T, K, float(domain), model[0], ctypes.byref(chunks),
+                                       plan))
+    if route < 0:
+        raise ValueError("ilrma_route: bad shape")
+    return route, int(chunks.value), tuple(plan)
+
+
 def ilrma_partition_expand(basis, activation, latent, Teff, Vrep):
     B, N, F, K = Teff.shape
     T = Vrep.shape[-1]

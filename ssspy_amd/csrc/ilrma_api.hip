@@ -1369,6 +1369,32 @@ int ssspy_ilrma_ip1_update_loss_slots(const void *X, const void *C, void *W, dou
                          info, slots, logdet, stream, slot_stride);
 }
 
+// the branch order of update_basis_impl / update_activation_impl, from their own predicates
+int ssspy_ilrma_route(int B, int N, int F, int T, int K, double domain, int source_model,
+                      int *chunks_out, int *basis_plan) {
+  if (B <= 0 || N < 2 || N > SSSPY_RT_MAX_SOURCES || F <= 0 || T <= 0 || K < 1 ||
+      K > SSSPY_MAX_BASIS || !(domain > 0.0 && domain <= 2.0))
+    return -1;
+  if (chunks_out) *chunks_out = act_chunks(B, N, F, T, K);
+  if (basis_plan) {
+    basis_plan[0] = basis_plan[1] = 0;
+    basis_plan[2] = 1;
+    if (N <= 4 && K <= 32 && fast_path(N, F, T, K, domain, source_model)) {
+      const TailPlan plan = ilrma_basis_plan(B, F, T, K);
+      basis_plan[0] = plan.full;
+      basis_plan[1] = plan.tail;
+      basis_plan[2] = plan.split;
+    }
+  }
+  if (rt_sources_ok(N)) return SSSPY_ROUTE_RUNTIME_N;
+  if (grouped_path(B, N, F, T, K, domain, source_model)) return SSSPY_ROUTE_GROUPED;
+  if (small_path(B, N, F, T, K, domain, source_model)) return SSSPY_ROUTE_LATENCY;
+  if (wide_basis_shape(N, K) && !(fast_path(N, F, T, K, domain, source_model) && K <= 32))
+    return SSSPY_ROUTE_WIDE_BASIS;
+  if (fast_path(N, F, T, K, domain, source_model)) return SSSPY_ROUTE_THROUGHPUT;
+  return SSSPY_ROUTE_GENERIC;
+}
+
 size_t ssspy_fold_scalar_slots_workspace_bytes(long long total, int nslots) {
   if (total <= 0 || nslots <= 0) return 0;
   return align256(fold_scratch_bytes(total, nslots)) + 256;

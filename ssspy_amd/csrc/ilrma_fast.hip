@@ -1232,15 +1232,8 @@ int LAUNCHER(ilrma_fast_basis)(const void *X, const void *W, const double *basis
     return fail(SSSPY_ERR_BADARG, "ilrma_fast_basis: power input excludes a filter and the loss");
   if (loss_out && !loss_ws) return fail(SSSPY_ERR_BADARG, "ilrma_fast_basis: loss without scratch");
   const int ktiles = K > 32 ? 4 : (K > 16 ? 2 : 1);
-#ifdef SSSPY_KTILE_ITEMS
-  const int item_tiles = ktiles;  // one item per (bin group, k tile)
-#else
-  const int item_tiles = ktiles == 2 ? 1 : ktiles;  // n_basis <= 32: both k tiles inside the item
-#endif
-  // (the wide variants hold one workgroup per CU)
-  const TailPlan plan =
-      make_tail_plan(B, ((F + 63) / 64) * item_tiles, (T + 15) / 16, ktiles >= 2 ? 256 : SLOTS,
-                     ktiles >= 2 ? 256 : 1024);  // (basis_part_bytes(): 1024 records)
+  const TailPlan plan = ilrma_basis_plan(B, F, T, K);
+  const int item_tiles = plan.groups / ((F + 63) / 64);  // k tiles that are items of their own
   const FastModel fm = make_fast_model(fmodel, mparam, me);
   dim3 grid(plan.full + plan.tail * plan.split), block(256);
   // loss slots per mixture: (bin group, chunk, wave) of the pass, then (bin group, block, wave) of

@@ -64,6 +64,20 @@ static inline TailPlan make_tail_plan(int B, int groups, int ntiles, int slots =
   return p;
 }
 
+// The plan of the tuned ILRMA basis pass (ilrma_fast.hip): an item is a bin group of 64 bins (one per
+// k tile above 32 bases); the wide variants (n_basis > 16) hold one workgroup per CU and have room
+// for 256 partial-sum records, the others for 1024 (basis_part_bytes() of ilrma_api.hip).
+static inline TailPlan ilrma_basis_plan(int B, int F, int T, int K) {
+  const int ktiles = K > 32 ? 4 : (K > 16 ? 2 : 1);
+#ifdef SSSPY_KTILE_ITEMS
+  const int item_tiles = ktiles;  // one item per (bin group, k tile)
+#else
+  const int item_tiles = ktiles == 2 ? 1 : ktiles;  // n_basis <= 32: both k tiles inside the item
+#endif
+  return make_tail_plan(B, ((F + 63) / 64) * item_tiles, (T + 15) / 16, ktiles >= 2 ? 256 : SLOTS,
+                        ktiles >= 2 ? 256 : 1024);
+}
+
 struct BlockWork {
   int b, group, chunk, nchunks, tail_idx;
 };
