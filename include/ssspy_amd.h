@@ -92,7 +92,7 @@ const char *ssspy_amd_version(void);
  *    ssspy_ilrma_loss_workspace_bytes / ssspy_fastmnmf_diagonalizer_covariance).
  * 3: round 6 (ssspy_ilrma_ip1_update_loss_slots: `logdet` became slots,
  *    ssspy_ilrma_deferred_logdet_slots added). */
-#define SSSPY_ABI_VERSION 3
+#define SSSPY_ABI_VERSION 4
 int ssspy_abi_version(void);
 const char *ssspy_last_error(void);
 
@@ -611,6 +611,53 @@ int ssspy_iva_grad_step_logdet_slots(int B, int F, int N);
 int ssspy_iva_grad_step(void *W, const void *stats, int stats_ready, int B, int F, int N,
                         int natural, int holonomic, double step_size, int *info, double *logdet,
                         long long logdet_stride, void *stream);
+
+/* ------------------------------------------------------------------ cACGMM */
+
+/* The EM iteration of CACGMM (complex angular central Gaussian mixture model) for B mixtures of M
+ * = 2..8 channels, N = 1..16 components (the count at run time), F bins, T frames; SSSPY_ERR_UNSUPPORTED
+ * outside.  Layouts: X, Z (B,M,F,T) complex; mixing (B,N,F); covariance (B,N,F,M,M) complex; posterior
+ * (B,N,F,T) real; binv (B,N,F,M*M) real: the inverse covariance packed as [M diagonal][re, im of the
+ * upper triangle, row-major]; logp (B,N,F) = log mixing - log det covariance.  Nothing here uses
+ * atomics on doubles: every sum has a fixed order and the results are the same bits on every run.
+ * replaces: ssspy/bss/cacgmm.py:141-145, :207-222, :561-601, :629-738. */
+
+/* Z = X / floor(||x_ij||_2) */
+int ssspy_cacgmm_unit_input(const void *X, void *Z, int B, int M, int F, int T, int floor_kind,
+                            double floor_eps, void *stream);
+
+/* binv and logp of the given parameters (Cholesky on the upper triangle; a pivot that is not positive
+ * bumps info[0], which may be NULL) */
+int ssspy_cacgmm_prepare(const void *covariance, const double *mixing, double *binv, double *logp,
+                         int B, int N, int F, int M, int *info, void *stream);
+
+/* One pass over Z with the parameters staged by ssspy_cacgmm_prepare:
+ *   q_nij = floor(max(Re z^H B_in^-1 z, 0)),  gamma = softmax_n(logp_in - M log q_nij)
+ *   sum_gamma[b,n,i] = sum_j gamma,  num[b,n,i] = sum_j (gamma / q) z z^H   (both or neither)
+ *   loss[b,i] = -(1/T) sum_j logsumexp_n(logp_in - M log q_nij)   (sum over i: CACGMM.compute_loss)
+ *   posterior[b,n,i,j] = gamma
+ * Each output may be NULL and is then not computed / not written.  posterior_in (may be NULL): the
+ * sums take these posteriors instead of the pass's own softmax. */
+int ssspy_cacgmm_frame_pass(const void *Z, const double *binv, const double *logp, int B, int M,
+                            int N, int F, int T, int floor_kind, double floor_eps,
+                            double *sum_gamma, void *num, double *loss, double *posterior,
+                            const double *posterior_in, void *stream);
+
+/* mixing = sum_gamma / T; covariance = to_psd(M num / sum_gamma) with the floor on the eigenvalues
+ * (ssspy_to_psd), divided by its real trace when normalize != 0.  num is overwritten. */
+int ssspy_cacgmm_parameter_step(const double *sum_gamma, void *num, double *mixing, void *covariance,
+                                int B, int N, int F, int M, int T, int floor_kind, double floor_eps,
+                                int normalize, void *stream);
+
+/* covariance <- covariance / Re tr covariance, in place */
+int ssspy_cacgmm_normalize(void *covariance, int B, int N, int F, int M, void *stream);
+
+/* out[r] = sum_i terms[r * F + i], r < rows, in a fixed order (the per-bin losses of the pass) */
+int ssspy_cacgmm_fold_loss(const double *terms, double *out, long long rows, int F, void *stream);
+
+/* out[b,n,i,j] = posterior[b,n,i,j] X[b,reference_id,i,j] */
+int ssspy_cacgmm_separate(const double *posterior, const void *X, void *out, int B, int N, int M,
+                          int F, int T, int reference_id, void *stream);
 
 /* ------------------------------------------------------------------ FastGaussMNMF (IP1) */
 

@@ -29,7 +29,7 @@ MAX_PAIRS = 32
 # the shared operators, ILRMA, AuxIVA, FastGaussMNMF's channels and sources, GaussMNMF's sources),
 # SSSPY_MAX_BASIS
 MAX_SOURCES, RT_MAX_SOURCES, MAX_BASIS = 8, 16, 65536
-ABI_VERSION = 3  # SSSPY_ABI_VERSION of the include/ssspy_amd.h these prototypes mirror
+ABI_VERSION = 4  # SSSPY_ABI_VERSION of the include/ssspy_amd.h these prototypes mirror
 
 _p, _i, _d, _z = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_size_t
 _q = ctypes.c_longlong
@@ -116,6 +116,14 @@ PROTOTYPES = {
     "ssspy_iva_score_weight": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _d, _p]),
     "ssspy_iva_grad_step_logdet_slots": (_i, [_i, _i, _i]),
     "ssspy_iva_grad_step": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _d, _p, _p, _q, _p]),
+    "ssspy_cacgmm_unit_input": (_i, [_p, _p, _i, _i, _i, _i, _i, _d, _p]),
+    "ssspy_cacgmm_prepare": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p]),
+    "ssspy_cacgmm_frame_pass": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _d, _p, _p, _p, _p, _p,
+                                     _p]),
+    "ssspy_cacgmm_parameter_step": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _d, _i, _p]),
+    "ssspy_cacgmm_normalize": (_i, [_p, _i, _i, _i, _i, _p]),
+    "ssspy_cacgmm_fold_loss": (_i, [_p, _p, _q, _i, _p]),
+    "ssspy_cacgmm_separate": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "ssspy_gmnmf_workspace_bytes": (_z, [_i, _i, _i, _i, _i, _i]),
     "ssspy_gmnmf_update": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _d, _p, _z, _p]),
     "ssspy_gmnmf_loss_workspace_bytes": (_z, [_i, _i, _i]),

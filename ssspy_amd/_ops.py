@@ -959,3 +959,90 @@ def gmnmf_separate(X, basis, activation, spatial, reference_id, flooring, out=No
         "gmnmf_separate",
     )
     return out
+
+
+# ----------------------------------------------------------------------------- cACGMM
+def cacgmm_unit_input(X, flooring):
+    """Z = X / floor(||x||_2) per (bin, frame); X (B, M, F, T)."""
+    B, M, F, T = X.shape
+    Z = dv.empty((B, M, F, T), dv.c128, X.device)
+    _lib.check(_L().ssspy_cacgmm_unit_input(ptr(X), ptr(Z), B, M, F, T, int(flooring[0]),
+                                            float(flooring[1]), _st()), "cacgmm_unit_input")
+    return Z
+
+
+def cacgmm_prepare(covariance, mixing, info=None, binv=None, logp=None):
+    """(binv, logp): the packed inverse covariances (B, N, F, M * M) and log mixing - log det
+    covariance (B, N, F) that ``cacgmm_frame_pass`` stages."""
+    B, N, F, M, _ = covariance.shape
+    assert tuple(mixing.shape) == (B, N, F)
+    if binv is None:
+        binv = dv.empty((B, N, F, M * M), dv.f64, covariance.device)
+    if logp is None:
+        logp = dv.empty((B, N, F), dv.f64, covariance.device)
+    _lib.check(_L().ssspy_cacgmm_prepare(ptr(covariance), ptr(mixing), ptr(binv), ptr(logp), B, N, F,
+                                         M, ptr(info), _st()), "cacgmm_prepare")
+    return binv, logp
+
+
+def cacgmm_frame_pass(Z, binv, logp, flooring, sum_gamma=None, num=None, loss=None, posterior=None,
+                      posterior_in=None):
+    """One pass over the unit mixture Z (B, M, F, T) with the staged parameters: whichever of
+    sum_gamma (B, N, F), num (B, N, F, M, M) (the two together), loss (B, F) and posterior
+    (B, N, F, T) are given are filled.  ``posterior_in``: posteriors the sums take instead of the
+    pass's own."""
+    B, M, F, T = Z.shape
+    N = logp.shape[1]
+    assert tuple(binv.shape) == (B, N, F, M * M) and tuple(logp.shape) == (B, N, F)
+    assert sum_gamma is None or tuple(sum_gamma.shape) == (B, N, F)
+    assert num is None or tuple(num.shape) == (B, N, F, M, M)
+    assert loss is None or tuple(loss.shape) == (B, F)
+    assert posterior is None or tuple(posterior.shape) == (B, N, F, T)
+    assert posterior_in is None or tuple(posterior_in.shape) == (B, N, F, T)
+    _lib.check(_L().ssspy_cacgmm_frame_pass(ptr(Z), ptr(binv), ptr(logp), B, M, N, F, T,
+                                            int(flooring[0]), float(flooring[1]), ptr(sum_gamma),
+                                            ptr(num), ptr(loss), ptr(posterior), ptr(posterior_in),
+                                            _st()),
+               "cacgmm_frame_pass")
+
+
+def cacgmm_parameter_step(sum_gamma, num, n_frames, flooring, normalize, mixing=None, covariance=None):
+    """(mixing, covariance) from the sums of a frame pass; ``num`` is overwritten."""
+    B, N, F, M, _ = num.shape
+    if mixing is None:
+        mixing = dv.empty((B, N, F), dv.f64, num.device)
+    if covariance is None:
+        covariance = dv.empty((B, N, F, M, M), dv.c128, num.device)
+    _lib.check(_L().ssspy_cacgmm_parameter_step(ptr(sum_gamma), ptr(num), ptr(mixing), ptr(covariance),
+                                                B, N, F, M, int(n_frames), int(flooring[0]),
+                                                float(flooring[1]), int(bool(normalize)), _st()),
+               "cacgmm_parameter_step")
+    return mixing, covariance
+
+
+def cacgmm_normalize(covariance):
+    """covariance / Re tr covariance, in place; (B, N, F, M, M)."""
+    B, N, F, M, _ = covariance.shape
+    _lib.check(_L().ssspy_cacgmm_normalize(ptr(covariance), B, N, F, M, _st()), "cacgmm_normalize")
+    return covariance
+
+
+def cacgmm_fold_loss(terms, out=None):
+    """out[...] = sum over the last axis of ``terms`` in a fixed order."""
+    F = terms.shape[-1]
+    rows = terms.numel() // F
+    if out is None:
+        out = dv.empty(tuple(terms.shape[:-1]), dv.f64, terms.device)
+    _lib.check(_L().ssspy_cacgmm_fold_loss(ptr(terms), ptr(out), rows, F, _st()), "cacgmm_fold_loss")
+    return out
+
+
+def cacgmm_separate(posterior, X, reference_id, out=None):
+    """out = posterior * X[:, reference_id]; posterior (B, N, F, T), X (B, M, F, T)."""
+    B, N, F, T = posterior.shape
+    M = X.shape[1]
+    if out is None:
+        out = dv.empty((B, N, F, T), dv.c128, X.device)
+    _lib.check(_L().ssspy_cacgmm_separate(ptr(posterior), ptr(X), ptr(out), B, N, M, F, T,
+                                          int(reference_id), _st()), "cacgmm_separate")
+    return out

@@ -1,4 +1,5 @@
-from . import base, ilrma, iva, mnmf
+from . import base, cacgmm, ilrma, iva, mnmf
 from .base import IterativeMethodBase
+from .cacgmm import CACGMM, CACGMMBase
 
-__all__ = ["IterativeMethodBase", "base", "ilrma", "iva", "mnmf"]
+__all__ = ["IterativeMethodBase", "CACGMM", "CACGMMBase", "base", "cacgmm", "ilrma", "iva", "mnmf"]
