@@ -478,6 +478,11 @@ int ssspy_fold_scalar_slots(const double *slots, long long total, int nslots, do
  *   THROUGHPUT  the tuned kernels of 2..4 sources (ilrma_fast.hip), n_basis <= 32
  *   GENERIC     the per-source-count kernels of any model (ilrma_kernels.hip)
  * (the basis update has no latency form: LATENCY shapes run the THROUGHPUT basis kernel.)
+ * The value is a summary of the launch plan every pass obeys (csrc/ilrma_plan.hpp), not a pass's own
+ * route: RUNTIME_N says that covariance, IP1, normalisation and loss run the run-time-N kernels; the
+ * basis / activation updates of such a shape run GROUPED (n_basis <= 32, a model of the tuned
+ * kernels) or WIDE_BASIS.  LATENCY covers the activation update, covariance fold, IP1 and
+ * normalisation.  The loss pass has its own split: tuned to 16 bases, dense products above.
  * *act_chunks (may be NULL): the number of bin chunks the activation pass of the THROUGHPUT, GROUPED
  * and GENERIC routes folds (1: no partial sums).
  * basis_plan (may be NULL): three ints on the frame splits of the basis pass on the LATENCY and

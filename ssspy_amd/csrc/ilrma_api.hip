@@ -1,175 +1,9 @@
-// C-ABI entry points of the Gauss-ILRMA path: dispatch over n_sources to the per-N MFMA
-// translation units (ilrma_kernels.hip, built with -DSSSPY_N=n) plus the small
-// normalisation / weight kernels that do not depend on N at compile time.
-#include <cstdlib>
-
-#include "common.hpp"
-#include "ilrma_params.hpp"
-#include "tail_plan.hpp"
-#include "wide_n.hpp"
+// C-ABI entry points of the Gauss-ILRMA path: each builds the launch plan of ilrma_plan.hpp and
+// launches what it says (the per-N MFMA translation units, ilrma_kernels.hip built with -DSSSPY_N=n,
+// among them), plus the small normalisation / weight kernels that do not depend on N at compile time.
+#include "ilrma_plan.hpp"
 
 namespace ssspy {
-
-#define DECL_N(n)                                                                               \
-  int ilrma_basis_n##n(const void *, const void *, const double *, double *, const double *,   \
-                       IlrmaDims, hipStream_t);                                                \
-  int ilrma_activation_n##n(const void *, const void *, const double *, const double *, double *, \
-                            int, IlrmaDims, hipStream_t);                                      \
-  int ilrma_wcov_n##n(const void *, const void *, const double *, const double *, void *,       \
-                      IlrmaDims, hipStream_t);                                                 \
-  size_t ilrma_loss_ws_bytes_n##n(int, int);                                                   \
-  int ilrma_loss_n##n(const void *, const void *, const double *, const double *, double *,     \
-                      void *, IlrmaDims, hipStream_t);
-DECL_N(2) DECL_N(3) DECL_N(4) DECL_N(5) DECL_N(6) DECL_N(7) DECL_N(8)
-#undef DECL_N
-
-// throughput variants (ilrma_fast.hip): n_basis <= 64 (two / four k tiles above 16 / 32), n_sources <= 4, models
-// of fast_model_id()
-#define DECL_FAST(n)                                                                           \
-  int ilrma_fast_basis_n##n(const void *, const void *, const double *, double *, const double *, \
-                            int, int, int, int, int, double, double *, int, double, int,        \
-                            double *, void *, int, hipStream_t, long long);                     \
-  int ilrma_fast_basis_loss_slots_n##n(int, int, int);                                          \
-  size_t ilrma_fast_loss_ws_bytes_n##n(int, int);                                               \
-  int ilrma_fast_activation_n##n(const void *, const void *, const double *, double *,         \
-                                 double *, int, int, int, int, int, int, double, int,           \
-                                 hipStream_t, int *, int, int, double);                         \
-  int ilrma_fast_wcov_n##n(const void *, const void *, const double *, const double *, void *, \
-                           int, int, int, int, void *, int, double, int, double, hipStream_t,  \
-                           int *, int *);                                                      \
-  int ilrma_fast_loss_n##n(const void *, const void *, const double *, const double *, double *, \
-                           void *, int, int, int, int, int, double, hipStream_t);
-DECL_FAST(2) DECL_FAST(3) DECL_FAST(4)
-#undef DECL_FAST
-
-// latency variants for a handful of mixtures (ilrma_small.hip): n_basis <= 16, n_sources <= 4
-#define DECL_SMALL(n)                                                                           \
-  size_t ilrma_small_scratch_n##n(int, int, int, int);                                            \
-  int ilrma_small_activation_n##n(const void *, const void *, const double *, double *, int, int, \
-                                  int, int, int, double, double *, int, double, int,              \
-                                  hipStream_t);                                                   \
-  int ilrma_small_ip1_n##n(const void *, int, int, long long, const void *, void *, int, int, int, \
-                           double, double *, int *, hipStream_t);                                 \
-  int ilrma_small_ip1_logdet_n##n(const void *, int, int, long long, const void *, void *, int,   \
-                                  int, int, double, double *, int *, double *, long long,         \
-                                  hipStream_t);                                                   \
-  int ilrma_small_norm_n##n(void *, double *, const double *, int, int, int, double, int, double, \
-                            hipStream_t);
-DECL_SMALL(2) DECL_SMALL(3) DECL_SMALL(4)
-#undef DECL_SMALL
-
-#define ILRMA_FAST_DISPATCH(N_, fn, ...)             \
-  switch (N_) {                                      \
-    case 2: return fn##_n2(__VA_ARGS__);             \
-    case 3: return fn##_n3(__VA_ARGS__);             \
-    default: return fn##_n4(__VA_ARGS__);            \
-  }
-
-// the tuned kernels: n_sources <= 4, n_basis <= 16 and one of the models ilrma_fast.hip carries
-// (its FM_* ids): Gauss at domain 2 (MM or ME), 1 or any other value in (0, 2), Student-t and GGD
-// at domain 2;
-// `source_model` may carry the SSSPY_SOURCE_ME flag.  -1: generic kernels.
-static inline int fast_model_id(double domain, int source_model) {
-  const int base = source_model & 0xff;
-  const bool me = (source_model & SSSPY_SOURCE_ME) != 0;
-  if (domain == 2.0) {
-    if (base == SSSPY_SOURCE_GAUSS) return 0;
-    if (base == SSSPY_SOURCE_T) return 1;
-    if (base == SSSPY_SOURCE_GGD) return 2;
-  }
-  if (domain == 1.0 && base == SSSPY_SOURCE_GAUSS && !me) return 3;
-  // Gauss at any other domain in (0, 2): the powers R^((p+2)/p), R^(2/p) as exp2(e log2 R)
-  if (base == SSSPY_SOURCE_GAUSS && !me && domain > 0.0 && domain < 2.0) return 4;
-  return -1;
-}
-// what the tuned kernels take as their model parameter: dof (t), beta (GGD), the domain (id 4)
-static inline double fast_model_param(double domain, int source_model, double model_param) {
-  return fast_model_id(domain, source_model) == 4 ? domain : model_param;
-}
-// (one channel of a mixture must fit the 32-bit offset of a buffer descriptor: F T 16 bytes < 4 GiB)
-static inline bool fast_path(int N, int F, int T, int K, double domain,
-                             int source_model = SSSPY_SOURCE_GAUSS) {
-  static const bool disabled = std::getenv("SSSPY_AMD_NO_FAST") != nullptr;
-  return !disabled && fast_model_id(domain, source_model) >= 0 && N >= 2 && N <= 4 && K <= 64 &&
-         (long long)F * T * 16 < (1ll << 32);
-}
-static inline int is_me(int source_model) { return (source_model & SSSPY_SOURCE_ME) ? 1 : 0; }
-
-// The latency kernels (ilrma_small.hip) serve batches whose bin tiles do not fill the chip with the
-// throughput kernels' 64-bin work items: B * ceil(F / 16) <= 350, i.e. up to 5 mixtures of 1025 bins --
-// round 4: with the cost-based tail plan the throughput kernels win from 6 mixtures on, 29.7 k
-// against 27.4 k mixture-iterations/s at 9, benchmarks/batch_sweep.py; it was 640:
-// up to 9 mixtures of 1025 bins).
-static inline bool small_path(int B, int N, int F, int T, int K, double domain,
-                              int source_model = SSSPY_SOURCE_GAUSS) {
-  const long long max_items = 350;
-  return K <= 16 && fast_path(N, F, T, K, domain, source_model) &&
-         (long long)B * ((F + 15) / 16) <= max_items;
-}
-static inline size_t small_scratch(int B, int N, int F, int T, int K) {
-  switch (N) {
-    case 2: return ilrma_small_scratch_n2(B, F, T, K);
-    case 3: return ilrma_small_scratch_n3(B, F, T, K);
-    case 4: return ilrma_small_scratch_n4(B, F, T, K);
-    default: return 0;
-  }
-}
-
-// More than 4 sources on the tuned NMF passes: the multiplicative updates of source n need only
-// |y_n|^2 and (T_n, V_n), and (B, N, ...) tensors are (B N / G, G, ...) tensors in memory, so a wide
-// mixture is walked as N / G "mixtures" of G sources over the separated spectrogram y = W x (formed
-// once by ssspy_separate; the ISS / IPA state is y already).  Returns the group size G (4, 3 or 2)
-// or 0 when the shape has none (N <= 4, N = 5 or 7, or the model / n_basis is off the tuned path).
-static inline int source_group(int N, int F, int T, int K, double domain, int source_model) {
-  if (N <= 4) return 0;
-  for (int G = 4; G >= 2; --G)
-    if (N % G == 0 && fast_path(G, F, T, K, domain, source_model)) return G;
-  return 0;
-}
-
-// shapes that may take the wide-basis path of wide_basis.hip (its buffers are sized for them; the
-// source model, which the workspace query does not know, decides at the call)
-// The register-tiled passes win up to 32 bases (16: 1.0 ms, 32: 1.6 ms per iteration at 32 mixtures of
-// the configs[1] shape); from 33 on their four-k-tile form (4.1-4.7 ms) loses to the dense products
-// (3.1-3.2 ms; 80: 4.1, 128: 4.6, 256: 7.1, 1024: 22.8 -- benchmarks/wide_basis.py, round 4).
-static inline bool wide_basis_shape(int N, int K) {
-  return K >= 33 || N > SSSPY_MAX_SOURCES;
-}
-// The general form (any source count above 4, e.g. 5 or 7): the B N sources of the batch, in memory
-// order, are cut into at most three runs of `count` groups of G sources each -- groups of 4 and one
-// or two closing groups of 3 / 2 sources -- and every run is one launch of the tuned kernels on its
-// slice of y, T and V.  Returns the number of runs (0: not on the grouped path).
-struct SourceRun {
-  long long first;  // first source of the run in the flat (B N) order
-  int count, G;     // `count` groups of G sources
-};
-static inline int source_runs(int B, int N, int F, int T, int K, double domain, int source_model,
-                              SourceRun (&run)[3]) {
-  if (N <= 4) return 0;
-  if (K > 32 && wide_basis_shape(N, K)) return 0;  // the dense products win from 33 bases on
-  if (const int G = source_group(N, F, T, K, domain, source_model)) {
-    run[0] = SourceRun{0, B * (N / G), G};
-    return 1;
-  }
-  for (int G = 2; G <= 4; ++G)
-    if (!fast_path(G, F, T, K, domain, source_model)) return 0;
-  const long long S = (long long)B * N;  // >= 5
-  const int r = (int)(S % 4);
-  const int tail = r == 0 ? 0 : (r == 1 ? 5 : r);  // 5 = 3 + 2
-  int n = 0;
-  if (S - tail > 0) run[n++] = SourceRun{0, (int)((S - tail) / 4), 4};
-  if (tail == 5) {
-    run[n++] = SourceRun{S - 5, 1, 3};
-    run[n++] = SourceRun{S - 2, 1, 2};
-  } else if (tail) {
-    run[n++] = SourceRun{S - tail, 1, tail};
-  }
-  return n;
-}
-static inline bool grouped_path(int B, int N, int F, int T, int K, double domain, int source_model) {
-  SourceRun run[3];
-  return source_runs(B, N, F, T, K, domain, source_model, run) > 0;
-}
 
 static inline int check_model(int source_model, double param, double domain = 2.0) {
   const int model = source_model & 0xff;
@@ -184,107 +18,23 @@ static inline int check_model(int source_model, double param, double domain = 2.
   return fail(SSSPY_ERR_BADARG, "bad source model / model_param (t: dof > 0, GGD: 0 < beta < 2)");
 }
 
-#define ILRMA_DISPATCH(N_, fn, ...)                                                  \
-  switch (N_) {                                                                      \
-    case 2: return fn##_n2(__VA_ARGS__);                                             \
-    case 3: return fn##_n3(__VA_ARGS__);                                             \
-    case 4: return fn##_n4(__VA_ARGS__);                                             \
-    case 5: return fn##_n5(__VA_ARGS__);                                             \
-    case 6: return fn##_n6(__VA_ARGS__);                                             \
-    case 7: return fn##_n7(__VA_ARGS__);                                             \
-    case 8: return fn##_n8(__VA_ARGS__);                                             \
-    default: return fail(SSSPY_ERR_UNSUPPORTED, "ILRMA: n_sources must be in [2, 8]"); \
-  }
-
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-static inline int ngroups_of(int N) { return N <= 4 ? 1 : (N + 1) / 2; }
-
-// number of bin chunks the activation pass splits into (partials are summed by the finalize
-// kernel): enough blocks to occupy the chip for small batches, one chunk for large ones.
-static inline int act_chunks(int B, int N, int F, int T, int K) {
-  const long long blocks0 = (long long)B * ngroups_of(N) * ((T + 63) / 64) * ((K + 15) / 16);
-  const int ntiles = (F + 15) / 16;
-  // (round 4: chunk count by the cost search of tail_plan.hpp instead of "just fill one round";
-  //  24 mixtures of the configs[1] shape: 5 chunks in two short rounds instead of 3 in two long ones)
-  const int want = best_split(blocks0, ntiles, 512, 16, 2048);
-  // a single chunk finishes in place (no partial sums): keep it whenever the batch fills the chip
-  return blocks0 >= 2048 ? 1 : want;
-}
-
-// (the latency kernel's partials when the shape can take it: the workspace is sized without knowing
-// the source model, so Gauss at domain 2 stands for "any model of the tuned path")
-static inline size_t act_part_bytes(int B, int N, int F, int T, int K) {
-  const size_t ap = (N >= 2 && N <= 4 && small_path(B, N, F, T, K, 2.0)) ? small_scratch(B, N, F, T, K) : 0;
-  const size_t base = (size_t)B * act_chunks(B, N, F, T, K) * N * 2 * K * T * sizeof(double);
-  return align256(base > ap ? base : ap);
-}
-static inline size_t basis_tmp_bytes(int B, int N, int F, int K) {
-  return K > 16 ? align256((size_t)B * N * F * K * sizeof(double)) : 0;
-}
-static inline size_t qbuf_bytes(int B, int N, int F) {
-  return align256((size_t)B * F * N * sizeof(double));
-}
-
 int ip1_with_power(void *W, const void *U, const void *C, double *qbuf, int B, int F, int N,
                    int floor_kind, double floor_eps, int *info, hipStream_t st);
 int separate_power(const void *X, const void *W, double *P, int B, int N, int F, int T,
                    hipStream_t st);
-// wide_cov.hip: weighted covariance of 5..8 channels on the matrix cores
-bool wide_weighted_cov_ok(int N, int S, int F, int T, int kind);
-int wide_weighted_cov(const void *A, const double *weight, int kind, void *U, int B, int N, int S,
-                      int F, int T, hipStream_t st);
-
-// scratch of the bin-major fast kernels (basis, covariance): partial sums of the at most 1024
-// split blocks of the closing scheduling rounds (TailPlan in ilrma_fast.hip)
-// (wide mixtures run them in groups of at most 4 sources, see source_group())
-// (the wide variants, 16 < n_basis <= 64: at most 256 split blocks, each leaving one 16-k record per
-//  k tile it accumulates -- up to 4)
-static inline size_t basis_part_bytes(int N) {
-  const int G = N < 4 ? N : 4;
-  return align256((size_t)1024 * G * 64 * 16 * 2 * sizeof(double));
-}
-// scratch of the deterministic loss sums: the larger of what the tuned kernels (by-product of the
-// basis pass, loss pass) and the generic loss kernel need
-size_t wb_loss_ws_bytes(int B, int N, int F, int T);  // wide_basis.hip
-// K, with_filter: the wide-basis loss (n_basis above 16, or more than 8 sources) parks one slot per
-// 64 x 64 tile of every source and, when a filter is given, |W x|^2 (B N F T doubles) -- only
-// then (round 4 added both terms for every shape: 2.1 GB idle at the headline batch, twice)
-static inline size_t loss_slots_bytes(int B, int N, int F, int T, int K, bool with_filter) {
-  auto generic = [&]() -> size_t {
-    switch (N) {
-      case 2: return ilrma_loss_ws_bytes_n2(B, F);
-      case 3: return ilrma_loss_ws_bytes_n3(B, F);
-      case 4: return ilrma_loss_ws_bytes_n4(B, F);
-      case 5: return ilrma_loss_ws_bytes_n5(B, F);
-      case 6: return ilrma_loss_ws_bytes_n6(B, F);
-      case 7: return ilrma_loss_ws_bytes_n7(B, F);
-      case 8: return ilrma_loss_ws_bytes_n8(B, F);
-      default: return 0;
-    }
-  };
-  auto tuned = [&]() -> size_t {
-    switch (N) {
-      case 2: return ilrma_fast_loss_ws_bytes_n2(B, F);
-      case 3: return ilrma_fast_loss_ws_bytes_n3(B, F);
-      case 4: return ilrma_fast_loss_ws_bytes_n4(B, F);
-      default: return 0;
-    }
-  };
-  const size_t a = generic(), b = tuned();
-  size_t c = rt_sources_ok(N) ? rt_ilrma_loss_ws_bytes(B, N, F) : 0;
-  // (the wide-basis loss: one slot per 64 x 64 tile of every source; a y = W x buffer when a filter
-  //  is given)
-  if (K > 16 || rt_sources_ok(N)) {
-    const size_t g = align256(wb_loss_ws_bytes(B, N, F, T)) +
-                     (with_filter ? align256((size_t)B * N * F * T * sizeof(double)) : 0);
-    c = c > g ? c : g;
-  }
-  return align256(a > b ? (a > c ? a : c) : (b > c ? b : c));
-}
-static inline size_t u_part_bytes(int N) {
-  return N <= 4 ? align256((size_t)1024 * 64 * N * N * N * 2 * sizeof(double)) : 0;
-}
 int row_power(const void *W, const void *C, double *qbuf, int B, int F, int N, hipStream_t st);
+// wide_basis.hip
+int wb_update_basis(const double *a, const double *b, double *basis, const double *activation,
+                    double *nd, int BN, int F, int T, int K, const IlrmaDims &d, hipStream_t st);
+int wb_update_activation(const double *a, const double *b, const double *basis, double *activation,
+                         double *nd, int BN, int F, int T, int K, const IlrmaDims &d,
+                         hipStream_t st);
+int wb_tv_weights(int mode, const double *basis, const double *activation, const double *ypow,
+                  const void *y, double *out0, double *out1, int BN, int F, int T, int K,
+                  const IlrmaDims &d, hipStream_t st);
+int wb_loss_data(const double *basis, const double *activation, const double *ypow, const void *y,
+                 double *out, void *ws, int B, int N, int F, int T, int K, const IlrmaDims &d,
+                 hipStream_t st);
 
 // V <- floor(V * (sum_chunks num / sum_chunks den)^(p/(p+2)))
 __global__ __launch_bounds__(256) void k_ilrma_activation_finalize(double *act,
@@ -671,68 +421,10 @@ using namespace ssspy;
 
 extern "C" {
 
-// One scratch layout for every ILRMA entry point: callers pass the same buffer everywhere.
-struct IlrmaWs {
-  size_t act_part, btmp, qbuf, psi, lslots, bpart, upart, praw, ybuf, wbuf, gb, gnd, total;
-};
-static inline IlrmaWs ilrma_ws(int B, int N, int F, int T, int K) {
-  IlrmaWs w;
-  size_t off = 0;
-  w.act_part = off;
-  off += act_part_bytes(B, N, F, T, K);
-  w.btmp = off;
-  off += basis_tmp_bytes(B, N, F, K);
-  w.qbuf = off;
-  off += qbuf_bytes(B, N, F);
-  w.psi = off;
-  off += align256((size_t)B * N * sizeof(double));
-  w.lslots = off;  // per-wave shares of a loss, folded in a fixed order (no fp64 atomics)
-  off += loss_slots_bytes(B, N, F, T, K, true);
-  w.bpart = off;
-  off += basis_part_bytes(N);
-  w.upart = off;
-  off += u_part_bytes(N);
-  w.praw = off;  // (num, den) basis sums of the partitioned updates
-  off += align256((size_t)B * N * F * K * 2 * sizeof(double));
-  const bool wb = wide_basis_shape(N, K);
-  w.ybuf = off;  // y = W x of a wide mixture (more than 4 sources), see source_group()
-  off += (N > 4 || wb) ? align256((size_t)B * N * F * T * 2 * sizeof(double)) : 0;
-  w.wbuf = off;  // varphi (B, N, F, T) of a wide mixture's covariance pass (wide_cov.hip); a of wide_basis
-  off += (N > 4 || wb) ? align256((size_t)B * N * F * T * sizeof(double)) : 0;
-  w.gb = off;    // wide-basis path: b = 1 / R (B, N, F, T)
-  off += wb ? align256((size_t)B * N * F * T * sizeof(double)) : 0;
-  w.gnd = off;   // wide-basis path: (num, den) of the products
-  off += wb ? align256((size_t)2 * B * N * (F > T ? F : T) * K * sizeof(double)) : 0;
-  w.total = off;
-  return w;
-}
-
 size_t ssspy_ilrma_workspace_bytes(int B, int N, int F, int T, int K) {
   if (B <= 0 || N <= 0 || F <= 0 || T <= 0 || K <= 0) return 0;
   return ilrma_ws(B, N, F, T, K).total;
 }
-
-extern "C++" {
-namespace ssspy {  // wide_basis.hip
-int wb_update_basis(const double *a, const double *b, double *basis, const double *activation,
-                    double *nd, int BN, int F, int T, int K, const IlrmaDims &d, hipStream_t st);
-int wb_update_activation(const double *a, const double *b, const double *basis, double *activation,
-                         double *nd, int BN, int F, int T, int K, const IlrmaDims &d,
-                         hipStream_t st);
-int wb_tv_weights(int mode, const double *basis, const double *activation, const double *ypow,
-                  const void *y, double *out0, double *out1, int BN, int F, int T, int K,
-                  const IlrmaDims &d, hipStream_t st);
-int wb_loss_data(const double *basis, const double *activation, const double *ypow, const void *y,
-                 double *out, void *ws, int B, int N, int F, int T, int K, const IlrmaDims &d,
-                 hipStream_t st);
-}  // namespace ssspy
-}  // extern "C++"
-
-// a = numerator factor, b = 1 / R of the MM updates for the wide-basis path: |y|^2 from the filter
-// (ybuf), from a power input, or from y itself; the weight kernel's (a, b) mode writes wbuf / gb
-static int wb_weights(const void *X, const void *W, bool x_is_power, const double *basis,
-                      const double *activation, int N, const IlrmaDims &d, char *ws, size_t ybuf,
-                      size_t wbuf, size_t gb, hipStream_t st);
 
 static IlrmaDims make_dims(int B, int F, int T, int K, double domain, int model, double mparam,
                            int floor_kind, double floor_eps) {
@@ -740,104 +432,108 @@ static IlrmaDims make_dims(int B, int F, int T, int K, double domain, int model,
                    floor_kind, floor_eps, 0};
 }
 
-static int wb_weights(const void *X, const void *W, bool x_is_power, const double *basis,
-                      const double *activation, int N, const IlrmaDims &d, char *ws, size_t ybuf,
-                      size_t wbuf, size_t gb, hipStream_t st) {
-  const c128 *Y = nullptr;
-  const double *Ypow = nullptr;
-  if (W) {
-    int r = separate_power(X, W, (double *)(ws + ybuf), d.B, N, d.F, d.T, st);
-    if (r) return r;
-    Ypow = (const double *)(ws + ybuf);
-  } else if (x_is_power) {
-    Ypow = (const double *)X;
-  } else {
-    Y = (const c128 *)X;
-  }
-  // (T V as a tiled GEMM with the (a, b) map in its epilogue: the weight kernel's own walk fetches
-  //  both operands from memory at every k-step -- 1.75 ms against 0.45 at n_basis 128, 32 mixtures)
-  return wb_tv_weights(1, basis, activation, Ypow, Y, (double *)(ws + wbuf), (double *)(ws + gb),
-                       d.B * N, d.F, d.T, d.K, d, st);
+// what the grouped and wide-basis NMF routes read: the separated spectrogram handed in (ISS / IPA
+// state) or its power, or the power |W x|^2 formed here in ybuf (half the bytes of y)
+static int nmf_input(const void *X, const void *W, bool x_is_power, int N, const IlrmaDims &d,
+                     char *ws, const IlrmaWs &w, hipStream_t st, const char **Y, bool *power) {
+  *Y = W ? ws + w.ybuf : (const char *)X;
+  *power = W ? true : x_is_power;
+  return W ? separate_power(X, W, (double *)(ws + w.ybuf), d.B, N, d.F, d.T, st) : SSSPY_OK;
 }
 
-// Basis update; with loss_out (B zeroed doubles) the tuned kernel also leaves the data term of the loss
-// of the state at entry there.  Returns 1 (not an error code of the ABI) when loss_out was requested
-// but the shape takes the generic kernels, which have no such by-product: the caller then makes the
-// dedicated loss pass.
-static int update_basis_impl(const void *X, const void *W, double *basis, const double *activation,
-                             int B, int N, int F, int T, int K, double domain, int source_model,
-                             double model_param, int floor_kind, double floor_eps, void *workspace,
-                             size_t workspace_bytes, double *loss_out, bool *loss_done,
-                             void *stream, bool x_is_power = false, long long loss_stride = 0) {
-  // loss_stride > 0: loss_out is a raw slot array (see ilrma_fast_basis), tuned path only
-  // x_is_power (grouped path of a wide mixture only, W == NULL): X holds |y|^2 (B, N, F, T) f64
+// a = numerator factor, b = 1 / R of the MM updates for the wide-basis route, written to wbuf / gb
+static int wb_weights(const void *X, const void *W, bool x_is_power, const double *basis,
+                      const double *activation, int N, const IlrmaDims &d, char *ws,
+                      const IlrmaWs &w, hipStream_t st) {
+  const char *Y;
+  bool power;
+  int r = nmf_input(X, W, x_is_power, N, d, ws, w, st, &Y, &power);
+  if (r) return r;
+  // (T V as a tiled GEMM with the (a, b) map in its epilogue: the weight kernel's own walk fetches
+  //  both operands from memory at every k-step -- 1.75 ms against 0.45 at n_basis 128, 32 mixtures)
+  return wb_tv_weights(1, basis, activation, power ? (const double *)Y : nullptr,
+                       power ? nullptr : Y, (double *)(ws + w.wbuf), (double *)(ws + w.gb), d.B * N,
+                       d.F, d.T, d.K, d, st);
+}
+
+// varphi (B, N, F, T) by k_ilrma_iss_weight; `gauss2`: the instance of the Gauss model at domain 2,
+// which reads no spectrogram.  Y: y (B, N, F, T), or |y|^2 with y_is_power
+static int launch_iss_weight(bool gauss2, const void *Y, bool y_is_power, const double *basis,
+                             const double *activation, double *varphi, int N, const IlrmaDims &d,
+                             hipStream_t st) {
+  const int chunks = iss_weight_chunks(d.B, N, d.F, d.T);
+  dim3 grid(((d.F + 63) / 64) * chunks, N, d.B), block(256);
+  if (gauss2)
+    hipLaunchKernelGGL(k_ilrma_iss_weight<true>, grid, block, 0, st, (const c128 *)nullptr,
+                       (const double *)nullptr, basis, activation, varphi, N, d, chunks,
+                       (double *)nullptr);
+  else
+    hipLaunchKernelGGL(k_ilrma_iss_weight<false>, grid, block, 0, st,
+                       y_is_power ? nullptr : (const c128 *)Y,
+                       y_is_power ? (const double *)Y : nullptr, basis, activation, varphi, N, d,
+                       chunks, (double *)nullptr);
+  return check_launch("k_ilrma_iss_weight");
+}
+
+// the argument checks of ssspy_ilrma_update_basis; ip1_update makes them before its basis pass
+static int check_basis_args(const void *X, const double *basis, const double *activation, int B,
+                            int F, int T, int K, double domain, int source_model,
+                            double model_param) {
   SSSPY_REQUIRE(X && basis && activation && B > 0 && F > 0 && T > 0, "update_basis: bad argument");
   SSSPY_REQUIRE(K >= 1 && K <= SSSPY_MAX_BASIS, "update_basis: n_basis must be in [1, 65536]");
   SSSPY_REQUIRE(domain > 0.0 && domain <= 2.0, "update_basis: domain must be in (0, 2]");
-  int rc = check_model(source_model, model_param, domain);
-  if (rc) return rc;
-  const IlrmaWs w = ilrma_ws(B, N, F, T, K);
-  SSSPY_REQUIRE(workspace && workspace_bytes >= w.total, "update_basis: workspace too small");
-  char *ws = (char *)workspace;
-  hipStream_t st = as_stream(stream);
-  if (loss_done) *loss_done = false;
-  SSSPY_REQUIRE(!x_is_power || (!W && (grouped_path(B, N, F, T, K, domain, source_model) ||
-                                       wide_basis_shape(N, K))),
-                "update_basis: power input off the grouped / wide-basis path");
-  // above 16 bases the update cannot be in place (several items per bin group read the old basis)
-  double *out = K > 16 ? (double *)(ws + w.btmp) : basis;
-  bool in_place = false;
+  return check_model(source_model, model_param, domain);
+}
+
+// Basis update by the plan's NMF route.  x_is_power (routes with power_once, W == NULL): X holds
+// |y|^2 (B, N, F, T) f64.  loss_out (only with the plan's loss_byproduct, so on the tuned route):
+// the data term of the loss at entry -- B doubles, or raw slots with loss_stride > 0 (ilrma_fast_basis)
+static int basis_pass(const IlrmaPlan &p, const IlrmaWs &w, const IlrmaDims &d, const void *X,
+                      const void *W, bool x_is_power, double *basis, const double *activation,
+                      char *ws, double *loss_out, long long loss_stride, hipStream_t st) {
+  const int B = d.B, N = p.N, F = d.F, T = d.T, K = d.K;
+  double *out = p.basis_out_of_place ? (double *)(ws + w.btmp) : basis;
+  double *bpart = (double *)(ws + w.bpart);
   auto run = [&]() -> int {
-    SourceRun runs[3];
-    if (const int nruns = source_runs(B, N, F, T, K, domain, source_model, runs)) {
-      // what the tuned kernels read: the separated spectrogram handed in (ISS / IPA state), or the
-      // power |W x|^2 formed here (half the bytes of y)
-      const char *Y = (const char *)X;
-      bool power = x_is_power;
-      if (W) {
-        int r = separate_power(X, W, (double *)(ws + w.ybuf), B, N, F, T, st);
+    switch (p.nmf) {
+      case NmfRoute::Grouped: {
+        const char *Y;
+        bool power;
+        int r = nmf_input(X, W, x_is_power, N, d, ws, w, st, &Y, &power);
         if (r) return r;
-        Y = ws + w.ybuf;
-        power = true;
+        const size_t elem = power ? sizeof(double) : sizeof(c128);
+        for (int i = 0; i < p.nruns; ++i) {
+          const SourceRun &sr = p.runs[i];
+          auto one = [&]() -> int {
+            ILRMA_FAST_DISPATCH(sr.G, ilrma_fast_basis, Y + (size_t)sr.first * F * T * elem,
+                                nullptr, basis + sr.first * F * K, out + sr.first * F * K,
+                                activation + sr.first * K * T, sr.count, F, T, K, d.floor_kind,
+                                d.floor_eps, bpart, p.fm_id, p.fm_param, p.me, nullptr, nullptr,
+                                power ? 1 : 0, st, 0ll);
+          };
+          r = one();
+          if (r) return r;
+        }
+        return SSSPY_OK;
       }
-      const size_t elem = power ? sizeof(double) : sizeof(c128);
-      for (int i = 0; i < nruns; ++i) {
-        const SourceRun &sr = runs[i];
-        auto one = [&]() -> int {
-          ILRMA_FAST_DISPATCH(sr.G, ilrma_fast_basis, Y + (size_t)sr.first * F * T * elem, nullptr,
-                              basis + sr.first * F * K, out + sr.first * F * K,
-                              activation + sr.first * K * T, sr.count, F, T, K, floor_kind,
-                              floor_eps, (double *)(ws + w.bpart),
-                              fast_model_id(domain, source_model), fast_model_param(domain, source_model, model_param),
-                              is_me(source_model), nullptr, nullptr, power ? 1 : 0, st, 0ll);
-        };
-        const int r = one();
+      case NmfRoute::Tuned:
+        ILRMA_FAST_DISPATCH(N, ilrma_fast_basis, X, W, basis, out, activation, B, F, T, K,
+                            d.floor_kind, d.floor_eps, bpart, p.fm_id, p.fm_param, p.me, loss_out,
+                            ws + w.lslots, 0, st, loss_stride);
+      case NmfRoute::WideBasis: {
+        // dense products, in place
+        int r = wb_weights(X, W, x_is_power, basis, activation, N, d, ws, w, st);
         if (r) return r;
+        return wb_update_basis((const double *)(ws + w.wbuf), (const double *)(ws + w.gb), basis,
+                               activation, (double *)(ws + w.gnd), B * N, F, T, K, d, st);
       }
-      return SSSPY_OK;
+      default:
+        ILRMA_DISPATCH(N, ilrma_basis, X, W, basis, out, activation, d, st);
     }
-    if (fast_path(N, F, T, K, domain, source_model) && !(K > 32 && wide_basis_shape(N, K))) {
-      if (loss_done) *loss_done = loss_out != nullptr && K <= 16;
-      ILRMA_FAST_DISPATCH(N, ilrma_fast_basis, X, W, basis, out, activation, B, F, T, K, floor_kind,
-                          floor_eps, (double *)(ws + w.bpart), fast_model_id(domain, source_model),
-                          fast_model_param(domain, source_model, model_param), is_me(source_model),
-                          K <= 16 ? loss_out : nullptr, ws + w.lslots, 0, st, loss_stride);
-    }
-    const IlrmaDims d =
-        make_dims(B, F, T, K, domain, source_model, model_param, floor_kind, floor_eps);
-    if (wide_basis_shape(N, K)) {
-      // n_basis above 64 (or more than 8 sources off the grouped path): dense products, in place
-      int r = wb_weights(X, W, x_is_power, basis, activation, N, d, ws, w.ybuf, w.wbuf, w.gb, st);
-      if (r) return r;
-      in_place = true;
-      return wb_update_basis((const double *)(ws + w.wbuf), (const double *)(ws + w.gb), basis,
-                             activation, (double *)(ws + w.gnd), B * N, F, T, K, d, st);
-    }
-    ILRMA_DISPATCH(N, ilrma_basis, X, W, basis, out, activation, d, st);
   };
-  rc = run();
+  int rc = run();
   if (rc) return rc;
-  if (out != basis && !in_place) {
+  if (out != basis && p.nmf != NmfRoute::WideBasis) {
     hipError_t e = hipMemcpyAsync(basis, out, (size_t)B * N * F * K * sizeof(double),
                                   hipMemcpyDeviceToDevice, st);
     if (e != hipSuccess) return fail(SSSPY_ERR_HIP, hipGetErrorString(e));
@@ -849,42 +545,30 @@ int ssspy_ilrma_update_basis(const void *X, const void *W, double *basis, const 
                              int B, int N, int F, int T, int K, double domain, int source_model,
                              double model_param, int floor_kind, double floor_eps, void *workspace,
                              size_t workspace_bytes, void *stream) {
-  return update_basis_impl(X, W, basis, activation, B, N, F, T, K, domain, source_model, model_param,
-                           floor_kind, floor_eps, workspace, workspace_bytes, nullptr, nullptr,
-                           stream);
-}
-
-static int update_activation_impl(const void *X, const void *W, const double *basis,
-                                  double *activation, int B, int N, int F, int T, int K,
-                                  double domain, int source_model, double model_param,
-                                  int floor_kind, double floor_eps, void *workspace,
-                                  size_t workspace_bytes, void *stream, bool x_is_power) {
-  SSSPY_REQUIRE(X && basis && activation && B > 0 && F > 0 && T > 0,
-                "update_activation: bad argument");
-  SSSPY_REQUIRE(K >= 1 && K <= SSSPY_MAX_BASIS, "update_activation: n_basis must be in [1, 65536]");
-  int rc = check_model(source_model, model_param, domain);
+  int rc = check_basis_args(X, basis, activation, B, F, T, K, domain, source_model, model_param);
   if (rc) return rc;
   const IlrmaWs w = ilrma_ws(B, N, F, T, K);
-  SSSPY_REQUIRE(workspace && workspace_bytes >= w.total, "update_activation: workspace too small");
-  double *part = (double *)((char *)workspace + w.act_part);
-  const int chunks = act_chunks(B, N, F, T, K);
-  hipStream_t st = as_stream(stream);
+  SSSPY_REQUIRE(workspace && workspace_bytes >= w.total, "update_basis: workspace too small");
+  const IlrmaPlan p = make_ilrma_plan(B, N, F, T, K, domain, source_model, model_param);
   const IlrmaDims d = make_dims(B, F, T, K, domain, source_model, model_param, floor_kind, floor_eps);
-  SourceRun runs[3];
-  const int nruns = source_runs(B, N, F, T, K, domain, source_model, runs);
-  SSSPY_REQUIRE(!x_is_power || (!W && (nruns || wide_basis_shape(N, K))),
-                "update_activation: power input off the grouped / wide-basis path");
-  if (!nruns && small_path(B, N, F, T, K, domain, source_model)) {
+  return basis_pass(p, w, d, X, W, false, basis, activation, (char *)workspace, nullptr, 0,
+                    as_stream(stream));
+}
+
+// Activation update by the plan's NMF route; x_is_power as in basis_pass
+static int activation_pass(const IlrmaPlan &p, const IlrmaWs &w, const IlrmaDims &d, const void *X,
+                           const void *W, bool x_is_power, const double *basis, double *activation,
+                           char *ws, hipStream_t st) {
+  const int B = d.B, N = p.N, F = d.F, T = d.T, K = d.K;
+  double *part = (double *)(ws + w.act_part);
+  const int chunks = p.act_chunks;
+  if (p.act_latency) {
     // a handful of mixtures: the latency kernel and its own fold (in place)
-    ILRMA_FAST_DISPATCH(N, ilrma_small_activation, X, W, basis, activation, B, F, T, K, floor_kind,
-                        floor_eps, part, fast_model_id(domain, source_model), fast_model_param(domain, source_model, model_param),
-                        is_me(source_model), st);
+    ILRMA_FAST_DISPATCH(N, ilrma_small_activation, X, W, basis, activation, B, F, T, K,
+                        d.floor_kind, d.floor_eps, part, p.fm_id, p.fm_param, p.me, st);
   }
-  if (!nruns && wide_basis_shape(N, K) &&
-      !(fast_path(N, F, T, K, domain, source_model) && K <= 32)) {
-    // n_basis above 64 (or more than 8 sources off the grouped path): dense products (wide_basis.hip)
-    char *ws = (char *)workspace;
-    rc = wb_weights(X, W, x_is_power, basis, activation, N, d, ws, w.ybuf, w.wbuf, w.gb, st);
+  if (p.nmf == NmfRoute::WideBasis) {
+    int rc = wb_weights(X, W, x_is_power, basis, activation, N, d, ws, w, st);
     if (rc) return rc;
     return wb_update_activation((const double *)(ws + w.wbuf), (const double *)(ws + w.gb), basis,
                                 activation, (double *)(ws + w.gnd), B * N, F, T, K, d, st);
@@ -892,61 +576,46 @@ static int update_activation_impl(const void *X, const void *W, const double *ba
   // (the partial sums of a run keep the (group, chunk, source) layout at the run's offset: every
   // source owns `chunks` slabs of 2 K T doubles wherever its group starts)
   const size_t part_per_source = (size_t)chunks * 2 * K * T;
-  // One chunk on the tuned kernels at n_basis <= 16: every work item holds the complete sums of its
-  // frames and can apply the update itself (k_activation_fast): no record of partial sums, no
-  // finalize launch; the launcher says whether it did.  The wider k ranges and the grouped runs of a
-  // wide mixture keep the fold.
-  // (-DSSSPY_NO_ACT_INPLACE: the record and the fold throughout, for A / B runs)
-#ifdef SSSPY_NO_ACT_INPLACE
-  const bool offer = false;
-#else
-  const bool offer = !nruns && chunks == 1 && K <= 16 && fast_path(N, F, T, K, domain, source_model);
-#endif
+  // act_in_place: every work item of the tuned kernel holds the complete sums of its frames and can
+  // apply the update itself (k_activation_fast): no record, no finalize; the launcher says if it did
   int finished = 0;
   auto run = [&]() -> int {
-    if (nruns) {
-      const char *Y = (const char *)X;
-      bool power = x_is_power;
-      if (W) {
-        int r = separate_power(X, W, (double *)((char *)workspace + w.ybuf), B, N, F, T, st);
+    switch (p.nmf) {
+      case NmfRoute::Grouped: {
+        const char *Y;
+        bool power;
+        int r = nmf_input(X, W, x_is_power, N, d, ws, w, st, &Y, &power);
         if (r) return r;
-        Y = (const char *)workspace + w.ybuf;
-        power = true;
+        const size_t elem = power ? sizeof(double) : sizeof(c128);
+        for (int i = 0; i < p.nruns; ++i) {
+          const SourceRun &sr = p.runs[i];
+          auto one = [&]() -> int {
+            ILRMA_FAST_DISPATCH(sr.G, ilrma_fast_activation, Y + (size_t)sr.first * F * T * elem,
+                                nullptr, basis + sr.first * F * K, activation + sr.first * K * T,
+                                part + sr.first * part_per_source, chunks, sr.count, F, T, K,
+                                p.fm_id, p.fm_param, power ? 1 : 0, st, nullptr, 0, 0, 0.0);
+          };
+          r = one();
+          if (r) return r;
+        }
+        return SSSPY_OK;
       }
-      const size_t elem = power ? sizeof(double) : sizeof(c128);
-      for (int i = 0; i < nruns; ++i) {
-        const SourceRun &sr = runs[i];
-        auto one = [&]() -> int {
-          ILRMA_FAST_DISPATCH(sr.G, ilrma_fast_activation, Y + (size_t)sr.first * F * T * elem,
-                              nullptr, basis + sr.first * F * K, activation + sr.first * K * T,
-                              part + sr.first * part_per_source, chunks, sr.count, F, T, K,
-                              fast_model_id(domain, source_model), fast_model_param(domain, source_model, model_param), power ? 1 : 0, st,
-                              nullptr, 0, 0, 0.0);
-        };
-        const int r = one();
-        if (r) return r;
-      }
-      return SSSPY_OK;
+      case NmfRoute::Tuned:
+        ILRMA_FAST_DISPATCH(N, ilrma_fast_activation, X, W, basis, activation, part, chunks, B, F,
+                            T, K, p.fm_id, p.fm_param, 0, st, p.act_in_place ? &finished : nullptr,
+                            d.me, d.floor_kind, d.floor_eps);
+      default:
+        ILRMA_DISPATCH(N, ilrma_activation, X, W, basis, activation, part, chunks, d, st);
     }
-    if (fast_path(N, F, T, K, domain, source_model)) {
-      ILRMA_FAST_DISPATCH(N, ilrma_fast_activation, X, W, basis, activation, part, chunks, B, F, T,
-                          K, fast_model_id(domain, source_model), fast_model_param(domain, source_model, model_param), 0, st,
-                          offer ? &finished : nullptr, d.me, floor_kind, floor_eps);
-    }
-    ILRMA_DISPATCH(N, ilrma_activation, X, W, basis, activation, part, chunks, d, st);
   };
-  rc = run();
+  int rc = run();
   if (rc || finished) return rc;
-  // fold the chunks in the layout the kernel wrote: (mixture, chunk, source) of the regrouped batch
-  // when the wide-mixture path ran
-  if (!nruns) {
-    dim3 g2((unsigned)(((long long)K * T + 255) / 256), N, B);
-    hipLaunchKernelGGL(k_ilrma_activation_finalize, g2, dim3(256), 0, st, activation,
-                       (const double *)part, N, K, T, chunks, d);
-    return check_launch("k_ilrma_activation_finalize");
-  }
-  for (int i = 0; i < nruns; ++i) {
-    const SourceRun &sr = runs[i];
+  // fold the chunks in the layout the kernel wrote: (mixture, chunk, source), run by run of the
+  // regrouped batch on the grouped route
+  const SourceRun whole{0, B, N};
+  const bool grouped = p.nmf == NmfRoute::Grouped;
+  for (int i = 0; i < (grouped ? p.nruns : 1); ++i) {
+    const SourceRun &sr = grouped ? p.runs[i] : whole;
     dim3 g2((unsigned)(((long long)K * T + 255) / 256), sr.G, sr.count);
     hipLaunchKernelGGL(k_ilrma_activation_finalize, g2, dim3(256), 0, st,
                        activation + sr.first * K * T,
@@ -960,75 +629,57 @@ int ssspy_ilrma_update_activation(const void *X, const void *W, const double *ba
                                   double domain, int source_model, double model_param,
                                   int floor_kind, double floor_eps, void *workspace,
                                   size_t workspace_bytes, void *stream) {
-  return update_activation_impl(X, W, basis, activation, B, N, F, T, K, domain, source_model,
-                                model_param, floor_kind, floor_eps, workspace, workspace_bytes,
-                                stream, false);
+  SSSPY_REQUIRE(X && basis && activation && B > 0 && F > 0 && T > 0,
+                "update_activation: bad argument");
+  SSSPY_REQUIRE(K >= 1 && K <= SSSPY_MAX_BASIS, "update_activation: n_basis must be in [1, 65536]");
+  int rc = check_model(source_model, model_param, domain);
+  if (rc) return rc;
+  const IlrmaWs w = ilrma_ws(B, N, F, T, K);
+  SSSPY_REQUIRE(workspace && workspace_bytes >= w.total, "update_activation: workspace too small");
+  const IlrmaPlan p = make_ilrma_plan(B, N, F, T, K, domain, source_model, model_param);
+  const IlrmaDims d = make_dims(B, F, T, K, domain, source_model, model_param, floor_kind, floor_eps);
+  return activation_pass(p, w, d, X, W, false, basis, activation, (char *)workspace,
+                         as_stream(stream));
 }
 
-// U[b,i,n] for every model; `upart` is the fast path's scratch for split blocks.  Wide mixtures
-// (5..8 sources) go through the weights varphi = 1 / R~ (`wbuf`, (B, N, F, T)) and the matrix-core
-// covariance of wide_cov.hip; the heavy-tailed models need the separated spectrogram for that
-// (`Ysep`, or X itself when W is NULL) and keep the generic kernel without it.
-static int wcov_into(const void *X, const void *W, const double *basis, const double *activation,
-                     void *U, int N, const IlrmaDims &d, void *upart, double *wbuf,
-                     const void *Ysep, bool ysep_is_power, hipStream_t st) {
-  if (rt_sources_ok(N)) {
-    // more than 8 sources: varphi = 1 / R^(2/p) by the ISS weight kernel (run-time N), then the
-    // run-time covariance of wide_n.hip.  Gauss model, or any model with y at hand
-    const void *Y = Ysep ? Ysep : (W ? nullptr : X);
-    const bool ypow = Ysep && ysep_is_power;
-    if (!wbuf || !(d.model == SSSPY_SOURCE_GAUSS || Y))
-      return fail(SSSPY_ERR_UNSUPPORTED,
-                  "ILRMA above 8 sources: covariance weights need the Gauss model or the separated "
-                  "spectrogram");
-    const int chunks = iss_weight_chunks(d.B, N, d.F, d.T);
-    dim3 grid(((d.F + 63) / 64) * chunks, N, d.B), block(256);
-    if (d.model == SSSPY_SOURCE_GAUSS && d.p == 2.0)
-      hipLaunchKernelGGL(k_ilrma_iss_weight<true>, grid, block, 0, st, (const c128 *)nullptr,
-                         (const double *)nullptr, basis, activation, wbuf, N, d, chunks,
-                         (double *)nullptr);
-    else
-      hipLaunchKernelGGL(k_ilrma_iss_weight<false>, grid, block, 0, st,
-                         ypow ? nullptr : (const c128 *)Y, ypow ? (const double *)Y : nullptr, basis,
-                         activation, wbuf, N, d, chunks, (double *)nullptr);
-    int rc = check_launch("k_ilrma_iss_weight");
-    if (rc) return rc;
-    return rt_covariance(X, X, wbuf, SSSPY_WEIGHT_BIN_FRAME, U, d.B, N, N, d.F, d.T, st);
-  }
-  if (wbuf && d.K > 32 && wide_basis_shape(N, d.K) &&
-      (d.model == SSSPY_SOURCE_GAUSS || Ysep || !W)) {
-    // n_basis above 64: the weight kernel walks any n_basis on the matrix cores; the covariance is
-    // then the shared weighted-covariance operator (no T V inside it)
-    const void *Y = Ysep ? Ysep : (W ? nullptr : X);
-    const bool ypow = Ysep && ysep_is_power;
-    int rc = wb_tv_weights(2, basis, activation, ypow ? (const double *)Y : nullptr,
-                           ypow ? nullptr : Y, wbuf, nullptr, d.B * N, d.F, d.T, d.K, d, st);
-    if (rc) return rc;
-    return ssspy_weighted_covariance(X, wbuf, SSSPY_WEIGHT_BIN_FRAME, U, d.B, N, N, d.F, d.T, st);
-  }
-  if (N > 4 && wbuf && wide_weighted_cov_ok(N, N, d.F, d.T, SSSPY_WEIGHT_BIN_FRAME)) {
-    const void *Y = Ysep ? Ysep : (W ? nullptr : X);
-    const bool ypow = Ysep && ysep_is_power;
-    if (d.model == SSSPY_SOURCE_GAUSS || Y) {
-      const int chunks = iss_weight_chunks(d.B, N, d.F, d.T);
-      dim3 grid(((d.F + 63) / 64) * chunks, N, d.B), block(256);
-      if (d.model == SSSPY_SOURCE_GAUSS && d.p == 2.0)
-        hipLaunchKernelGGL(k_ilrma_iss_weight<true>, grid, block, 0, st, (const c128 *)nullptr,
-                           (const double *)nullptr, basis, activation, wbuf, N, d, chunks,
-                           (double *)nullptr);
-      else
-        hipLaunchKernelGGL(k_ilrma_iss_weight<false>, grid, block, 0, st,
-                           ypow ? nullptr : (const c128 *)Y, ypow ? (const double *)Y : nullptr,
-                           basis, activation, wbuf, N, d, chunks, (double *)nullptr);
+// U[b,i,n] for every model, by cov_route().  Ysep: the separated spectrogram, or its power, where
+// the caller has it; without a filter X is that spectrogram.
+static int wcov_into(const IlrmaPlan &p, const IlrmaWs &w, const IlrmaDims &d, const void *X,
+                     const void *W, const double *basis, const double *activation, void *U,
+                     char *ws, const void *Ysep, bool ysep_is_power, hipStream_t st) {
+  const int N = p.N;
+  double *wbuf = (double *)(ws + w.wbuf);  // (the routes that write weights have weights_buf)
+  const void *Y = Ysep ? Ysep : (W ? nullptr : X);
+  const bool ypow = Ysep && ysep_is_power;
+  const bool gauss2 = p.gauss && d.p == 2.0;
+  int rc;
+  switch (cov_route(p, Ysep != nullptr, W != nullptr)) {
+    case CovRoute::RuntimeN:
+      if (!(p.gauss || Y))
+        return fail(SSSPY_ERR_UNSUPPORTED,
+                    "ILRMA above 8 sources: covariance weights need the Gauss model or the separated "
+                    "spectrogram");
+      rc = launch_iss_weight(gauss2, Y, ypow, basis, activation, wbuf, N, d, st);
+      if (rc) return rc;
+      return rt_covariance(X, X, wbuf, SSSPY_WEIGHT_BIN_FRAME, U, d.B, N, N, d.F, d.T, st);
+    case CovRoute::WideBasis:
+      // the product kernel forms the weights at any n_basis; the covariance is then the shared
+      // weighted-covariance operator (no T V inside it)
+      rc = wb_tv_weights(2, basis, activation, ypow ? (const double *)Y : nullptr,
+                         ypow ? nullptr : Y, wbuf, nullptr, d.B * N, d.F, d.T, d.K, d, st);
+      if (rc) return rc;
+      return ssspy_weighted_covariance(X, wbuf, SSSPY_WEIGHT_BIN_FRAME, U, d.B, N, N, d.F, d.T, st);
+    case CovRoute::MatrixCore:
+      rc = launch_iss_weight(gauss2, Y, ypow, basis, activation, wbuf, N, d, st);
+      if (rc) return rc;
       return wide_weighted_cov(X, wbuf, SSSPY_WEIGHT_BIN_FRAME, U, d.B, N, N, d.F, d.T, st);
-    }
+    case CovRoute::Tuned:
+      ILRMA_FAST_DISPATCH(N, ilrma_fast_wcov, X, W, basis, activation, U, d.B, d.F, d.T, d.K,
+                          ws + w.upart, p.fm_id, p.fm_param, d.floor_kind, d.floor_eps, st, nullptr,
+                          nullptr);
+    default:
+      ILRMA_DISPATCH(N, ilrma_wcov, X, W, basis, activation, U, d, st);
   }
-  if (fast_path(N, d.F, d.T, d.K, d.p, d.model) && (d.model == SSSPY_SOURCE_GAUSS || W)) {
-    ILRMA_FAST_DISPATCH(N, ilrma_fast_wcov, X, W, basis, activation, U, d.B, d.F, d.T, d.K, upart,
-                        fast_model_id(d.p, d.model), fast_model_param(d.p, d.model, d.mparam), d.floor_kind, d.floor_eps, st,
-                        nullptr, nullptr);
-  }
-  ILRMA_DISPATCH(N, ilrma_wcov, X, W, basis, activation, U, d, st);
 }
 
 int ssspy_ilrma_weighted_covariance(const void *X, const void *W, const double *basis,
@@ -1044,19 +695,19 @@ int ssspy_ilrma_weighted_covariance(const void *X, const void *W, const double *
   const IlrmaWs w = ilrma_ws(B, N, F, T, K);
   SSSPY_REQUIRE(workspace && workspace_bytes >= w.total,
                 "ilrma_weighted_covariance: workspace too small");
+  char *ws = (char *)workspace;
   hipStream_t st = as_stream(stream);
+  const IlrmaPlan p = make_ilrma_plan(B, N, F, T, K, domain, source_model, model_param);
   const IlrmaDims d = make_dims(B, F, T, K, domain, source_model, model_param, floor_kind, floor_eps);
   // more than 8 sources with a heavy-tailed model: the run-time-N weights need |W x|^2 (the fused
   // IP1 iteration has it from its NMF passes; a caller of this entry alone -- IP2 -- has not)
   const void *Ysep = nullptr;
-  if (rt_sources_ok(N) && source_model != SSSPY_SOURCE_GAUSS && W) {
-    rc = separate_power(X, W, (double *)((char *)workspace + w.ybuf), B, N, F, T, st);
+  if (p.runtime_n && source_model != SSSPY_SOURCE_GAUSS && W) {
+    rc = separate_power(X, W, (double *)(ws + w.ybuf), B, N, F, T, st);
     if (rc) return rc;
-    Ysep = (const char *)workspace + w.ybuf;
+    Ysep = ws + w.ybuf;
   }
-  return wcov_into(X, W, basis, activation, U, N, d, (char *)workspace + w.upart,
-                   (N > 4 || wide_basis_shape(N, K)) ? (double *)((char *)workspace + w.wbuf) : nullptr,
-                   Ysep, Ysep != nullptr, st);
+  return wcov_into(p, w, d, X, W, basis, activation, U, ws, Ysep, Ysep != nullptr, st);
 }
 
 // qbuf (B, F, N) is consumed: psi replaces its first N values of every mixture (k_norm_psi)
@@ -1133,12 +784,7 @@ int ssspy_ilrma_iss_weight_power(const double *Ypow, const double *basis, const 
   int rc = check_model(source_model, model_param, domain);
   if (rc) return rc;
   const IlrmaDims d = make_dims(B, F, T, K, domain, source_model, model_param, floor_kind, floor_eps);
-  const int chunks = iss_weight_chunks(B, N, F, T);
-  dim3 grid(((F + 63) / 64) * chunks, N, B), block(256);
-  hipLaunchKernelGGL(k_ilrma_iss_weight<false>, grid, block, 0, as_stream(stream),
-                     (const c128 *)nullptr, Ypow, basis, activation, varphi, N, d, chunks,
-                     (double *)nullptr);
-  return check_launch("k_ilrma_iss_weight");
+  return launch_iss_weight(false, Ypow, true, basis, activation, varphi, N, d, as_stream(stream));
 }
 
 int ssspy_ilrma_iss_weight(const void *Y, const double *basis, const double *activation,
@@ -1150,22 +796,13 @@ int ssspy_ilrma_iss_weight(const void *Y, const double *basis, const double *act
   int rc = check_model(source_model, model_param, domain);
   if (rc) return rc;
   const IlrmaDims d = make_dims(B, F, T, K, domain, source_model, model_param, floor_kind, floor_eps);
-  const int chunks = iss_weight_chunks(B, N, F, T);
-  dim3 grid(((F + 63) / 64) * chunks, N, B), block(256);
-  if (source_model == SSSPY_SOURCE_GAUSS && domain == 2.0)
-    hipLaunchKernelGGL(k_ilrma_iss_weight<true>, grid, block, 0, as_stream(stream),
-                       (const c128 *)nullptr, (const double *)nullptr, basis, activation, varphi, N,
-                       d, chunks, (double *)nullptr);
-  else
-    hipLaunchKernelGGL(k_ilrma_iss_weight<false>, grid, block, 0, as_stream(stream), (const c128 *)Y,
-                       (const double *)nullptr, basis, activation, varphi, N, d, chunks,
-                       (double *)nullptr);
-  return check_launch("k_ilrma_iss_weight");
+  return launch_iss_weight(source_model == SSSPY_SOURCE_GAUSS && domain == 2.0, Y, false, basis,
+                           activation, varphi, N, d, as_stream(stream));
 }
 
 size_t ssspy_ilrma_loss_workspace_bytes(int B, int N, int F, int T, int K, int with_filter) {
   if (B <= 0 || N <= 0 || F <= 0 || T <= 0 || K <= 0) return 0;
-  return loss_slots_bytes(B, N, F, T, K, with_filter != 0);
+  return loss_slots_bytes(shape_plan(B, N, F, T, K), B, F, T, with_filter != 0);
 }
 
 int ssspy_ilrma_loss_data(const void *X, const void *W, const double *basis,
@@ -1175,34 +812,36 @@ int ssspy_ilrma_loss_data(const void *X, const void *W, const double *basis,
   SSSPY_REQUIRE(X && basis && activation && out && B > 0, "ilrma_loss_data: bad argument");
   SSSPY_REQUIRE(K >= 1 && K <= SSSPY_MAX_BASIS, "ilrma_loss_data: bad n_basis");
   SSSPY_REQUIRE(N >= 2 && N <= SSSPY_RT_MAX_SOURCES, "ilrma_loss_data: n_sources must be in [2, 16]");
-  SSSPY_REQUIRE(workspace && workspace_bytes >= loss_slots_bytes(B, N, F, T, K, W != nullptr),
+  const IlrmaPlan p = make_ilrma_plan(B, N, F, T, K, domain, source_model, model_param);
+  SSSPY_REQUIRE(workspace && workspace_bytes >= loss_slots_bytes(p, B, F, T, W != nullptr),
                 "ilrma_loss_data: workspace too small (ssspy_ilrma_loss_workspace_bytes)");
   int rc = check_model(source_model, model_param, domain);
   if (rc) return rc;
   hipStream_t st = as_stream(stream);
-  if (K <= 16 && fast_path(N, F, T, K, domain, source_model)) {
-    ILRMA_FAST_DISPATCH(N, ilrma_fast_loss, X, W, basis, activation, out, workspace, B, F, T, K,
-                        fast_model_id(domain, source_model), fast_model_param(domain, source_model, model_param), st);
-  }
-  if (K > 16 || rt_sources_ok(N)) {
-    // n_basis above 16 (or more than 8 sources): T V on the matrix cores, the terms summed in the
-    // product's epilogue (wide_basis.hip) -- the per-N loss kernels took 1.7 / 2.8 / 5.0 ms at
-    // n_basis 32 / 64 / 128 (32 mixtures), as much as the iteration they follow
-    const IlrmaDims dl = make_dims(B, F, T, K, domain, source_model, model_param, SSSPY_FLOOR_NONE, 0.0);
-    char *wsb = (char *)workspace;
-    const size_t slots = align256(wb_loss_ws_bytes(B, N, F, T));
-    const double *ypow = nullptr;
-    const void *y = X;
-    if (W) {
-      rc = separate_power(X, W, (double *)(wsb + slots), B, N, F, T, st);
-      if (rc) return rc;
-      ypow = (const double *)(wsb + slots);
-      y = nullptr;
-    }
-    return wb_loss_data(basis, activation, ypow, y, out, workspace, B, N, F, T, K, dl, st);
-  }
   const IlrmaDims d = make_dims(B, F, T, K, domain, source_model, model_param, SSSPY_FLOOR_NONE, 0.0);
-  ILRMA_DISPATCH(N, ilrma_loss, X, W, basis, activation, out, workspace, d, st);
+  switch (p.loss) {
+    case LossRoute::Tuned:
+      ILRMA_FAST_DISPATCH(N, ilrma_fast_loss, X, W, basis, activation, out, workspace, B, F, T, K,
+                          p.fm_id, p.fm_param, st);
+    case LossRoute::WideBasis: {
+      // T V on the matrix cores, the terms summed in the product's epilogue (wide_basis.hip) -- the
+      // per-N loss kernels took 1.7 / 2.8 / 5.0 ms at n_basis 32 / 64 / 128 (32 mixtures), as much
+      // as the iteration they follow
+      char *wsb = (char *)workspace;
+      const size_t slots = align256(wb_loss_ws_bytes(B, N, F, T));
+      const double *ypow = nullptr;
+      const void *y = X;
+      if (W) {
+        rc = separate_power(X, W, (double *)(wsb + slots), B, N, F, T, st);
+        if (rc) return rc;
+        ypow = (const double *)(wsb + slots);
+        y = nullptr;
+      }
+      return wb_loss_data(basis, activation, ypow, y, out, workspace, B, N, F, T, K, d, st);
+    }
+    default:
+      ILRMA_DISPATCH(N, ilrma_loss, X, W, basis, activation, out, workspace, d, st);
+  }
 }
 
 static int ip1_update_impl(const void *X, const void *C, void *W, double *basis, double *activation,
@@ -1217,66 +856,48 @@ static int ip1_update_impl(const void *X, const void *C, void *W, double *basis,
                 "ilrma_ip1_update: loss_data and logdet go together");
   const IlrmaWs w = ilrma_ws(B, N, F, T, K);
   SSSPY_REQUIRE(workspace && workspace_bytes >= w.total, "ilrma_ip1_update: workspace too small");
+  const IlrmaPlan p = make_ilrma_plan(B, N, F, T, K, domain, source_model, model_param);
   char *ws = (char *)workspace;
   hipStream_t st = as_stream(stream);
   int rc;
   if (loss_data) {
-    // (the Student-t data term is not linear in the pass's accumulators; no by-product there)
-    if (!ssspy_ilrma_deferred_loss_supported(N, F, T, K, domain, source_model))
+    if (!p.loss_byproduct)
       return fail(SSSPY_ERR_UNSUPPORTED,
                   "ilrma_ip1_update_deferred_loss: this shape takes the generic kernels, which have "
                   "no loss by-product (use ssspy_ilrma_loss_data + ssspy_ilrma_ip1_update)");
     // loss of the state at entry: log-determinants now (IP1 rewrites W below) -- or, with slots on
     // the latency path, as one share per 16-bin tile from the IP1 kernel itself, which reads the
     // same filters before it rewrites them -- data term as a by-product of the basis pass
-    if (!(loss_stride > 0 && small_path(B, N, F, T, K, domain, source_model))) {
+    if (!(loss_stride > 0 && p.ip1_latency)) {
       rc = ssspy_sum_logdet(W, logdet, B, F, N, stream);
       if (rc) return rc;
     }
     // (loss_data is stored, not accumulated: the basis pass folds its per-wave shares into it)
   }
-  bool loss_done = false;
-  // wide mixture on the grouped path: y = W x once for both NMF passes (they then see the ISS-style
-  // state: the spectrogram itself, no filter)
+  // the grouped and wide-basis NMF routes: |W x|^2 once for both NMF passes (they then see the
+  // ISS-style state: a spectrogram's power, no filter) and for the weights of the covariance pass
   const void *Xs = X, *Ws = W;
-  bool xs_is_power = false;
-  if (grouped_path(B, N, F, T, K, domain, source_model)) {
-    // (the passes that follow need |y|^2 only: the NMF passes, and the weights of a heavy-tailed
-    // covariance pass)
+  if (p.power_once) {
     rc = separate_power(X, W, (double *)(ws + w.ybuf), B, N, F, T, st);
     if (rc) return rc;
     Xs = ws + w.ybuf;
     Ws = nullptr;
-    xs_is_power = true;
-  } else if (wide_basis_shape(N, K) && !(K <= 32 && fast_path(N, F, T, K, domain, source_model))) {
-    // dense-product path (wide_basis.hip): |W x|^2 once for both source updates and the weights
-    rc = separate_power(X, W, (double *)(ws + w.ybuf), B, N, F, T, st);
-    if (rc) return rc;
-    Xs = ws + w.ybuf;
-    Ws = nullptr;
-    xs_is_power = true;
   }
-  rc = update_basis_impl(Xs, Ws, basis, activation, B, N, F, T, K, domain, source_model,
-                         model_param, floor_kind, floor_eps, workspace, workspace_bytes, loss_data,
-                         &loss_done, stream, xs_is_power, loss_stride);
+  rc = check_basis_args(Xs, basis, activation, B, F, T, K, domain, source_model, model_param);
   if (rc) return rc;
-  // (unreachable: ssspy_ilrma_deferred_loss_supported above admits exactly the shapes whose basis
-  // pass leaves the data term; kept as an internal error because the basis is already rewritten)
-  if (loss_data && !loss_done)
-    return fail(SSSPY_ERR_INTERNAL, "ilrma_ip1_update: basis pass left no loss by-product");
-  rc = update_activation_impl(Xs, Ws, basis, activation, B, N, F, T, K, domain, source_model,
-                              model_param, floor_kind, floor_eps, workspace, workspace_bytes, stream,
-                              xs_is_power);
+  const IlrmaDims d = make_dims(B, F, T, K, domain, source_model, model_param, floor_kind, floor_eps);
+  rc = basis_pass(p, w, d, Xs, Ws, p.power_once, basis, activation, ws, loss_data, loss_stride, st);
+  if (rc) return rc;
+  rc = activation_pass(p, w, d, Xs, Ws, p.power_once, basis, activation, ws, st);
   if (rc) return rc;
   double *qbuf = (double *)(ws + w.qbuf);
-  if (small_path(B, N, F, T, K, domain, source_model)) {
+  if (p.ip1_latency) {
     // a handful of mixtures: the covariance pass leaves its split items' records, and one kernel
     // folds them, runs IP1 and forms the output power; U is materialised only if no item was split
     int split = 0, rbins = 0;
     auto cov = [&]() -> int {
       ILRMA_FAST_DISPATCH(N, ilrma_fast_wcov, X, W, basis, activation, U, B, F, T, K, ws + w.upart,
-                          fast_model_id(domain, source_model), fast_model_param(domain, source_model, model_param), floor_kind, floor_eps,
-                          st, &split, &rbins);
+                          p.fm_id, p.fm_param, floor_kind, floor_eps, st, &split, &rbins);
     };
     rc = cov();
     if (rc) return rc;
@@ -1296,10 +917,8 @@ static int ip1_update_impl(const void *X, const void *C, void *W, double *basis,
     ILRMA_FAST_DISPATCH(N, ilrma_small_norm, W, basis, qbuf, B, F, K, domain, floor_kind, floor_eps,
                         st);
   }
-  const IlrmaDims d = make_dims(B, F, T, K, domain, source_model, model_param, floor_kind, floor_eps);
-  rc = wcov_into(X, W, basis, activation, U, N, d, ws + w.upart,
-                 (N > 4 || wide_basis_shape(N, K)) ? (double *)(ws + w.wbuf) : nullptr,
-                 Ws ? nullptr : Xs, xs_is_power, st);
+  rc = wcov_into(p, w, d, X, W, basis, activation, U, ws, p.power_once ? Xs : nullptr, p.power_once,
+                 st);
   if (rc) return rc;
   rc = ip1_with_power(W, U, normalize ? C : nullptr, normalize ? qbuf : nullptr, B, F, N,
                       floor_kind, floor_eps, info, st);
@@ -1319,8 +938,7 @@ int ssspy_ilrma_ip1_update(const void *X, const void *C, void *W, double *basis,
 
 int ssspy_ilrma_deferred_loss_supported(int N, int F, int T, int K, double domain,
                                         int source_model) {
-  return K <= 16 && fast_path(N, F, T, K, domain, source_model) &&
-         fast_model_id(domain, source_model) != 1;
+  return make_ilrma_plan(1, N, F, T, K, domain, source_model).loss_byproduct;
 }
 
 int ssspy_ilrma_ip1_update_deferred_loss(const void *X, const void *C, void *W, double *basis,
@@ -1340,19 +958,12 @@ int ssspy_ilrma_ip1_update_deferred_loss(const void *X, const void *C, void *W, 
 // iteration (3 of the 12 launches of a one-mixture iteration, 17 of its 124 us)
 int ssspy_ilrma_deferred_loss_slots(int B, int N, int F, int T, int K, double domain,
                                     int source_model) {
-  if (!ssspy_ilrma_deferred_loss_supported(N, F, T, K, domain, source_model)) return 0;
-  switch (N) {
-    case 2: return ilrma_fast_basis_loss_slots_n2(B, F, T);
-    case 3: return ilrma_fast_basis_loss_slots_n3(B, F, T);
-    case 4: return ilrma_fast_basis_loss_slots_n4(B, F, T);
-    default: return 0;
-  }
+  return make_ilrma_plan(B, N, F, T, K, domain, source_model).loss_slots;
 }
 
 int ssspy_ilrma_deferred_logdet_slots(int B, int N, int F, int T, int K, double domain,
                                       int source_model) {
-  if (!ssspy_ilrma_deferred_loss_supported(N, F, T, K, domain, source_model)) return 0;
-  return small_path(B, N, F, T, K, domain, source_model) ? (F + 15) / 16 : 1;
+  return make_ilrma_plan(B, N, F, T, K, domain, source_model).logdet_slots;
 }
 
 int ssspy_ilrma_ip1_update_loss_slots(const void *X, const void *C, void *W, double *basis,
@@ -1369,30 +980,20 @@ int ssspy_ilrma_ip1_update_loss_slots(const void *X, const void *C, void *W, dou
                          info, slots, logdet, stream, slot_stride);
 }
 
-// the branch order of update_basis_impl / update_activation_impl, from their own predicates
+// a projection of the plan the passes obey
 int ssspy_ilrma_route(int B, int N, int F, int T, int K, double domain, int source_model,
                       int *chunks_out, int *basis_plan) {
   if (B <= 0 || N < 2 || N > SSSPY_RT_MAX_SOURCES || F <= 0 || T <= 0 || K < 1 ||
       K > SSSPY_MAX_BASIS || !(domain > 0.0 && domain <= 2.0))
     return -1;
-  if (chunks_out) *chunks_out = act_chunks(B, N, F, T, K);
+  const IlrmaPlan p = make_ilrma_plan(B, N, F, T, K, domain, source_model);
+  if (chunks_out) *chunks_out = p.act_chunks;
   if (basis_plan) {
-    basis_plan[0] = basis_plan[1] = 0;
-    basis_plan[2] = 1;
-    if (N <= 4 && K <= 32 && fast_path(N, F, T, K, domain, source_model)) {
-      const TailPlan plan = ilrma_basis_plan(B, F, T, K);
-      basis_plan[0] = plan.full;
-      basis_plan[1] = plan.tail;
-      basis_plan[2] = plan.split;
-    }
+    basis_plan[0] = p.basis_tail.full;
+    basis_plan[1] = p.basis_tail.tail;
+    basis_plan[2] = p.basis_tail.split;
   }
-  if (rt_sources_ok(N)) return SSSPY_ROUTE_RUNTIME_N;
-  if (grouped_path(B, N, F, T, K, domain, source_model)) return SSSPY_ROUTE_GROUPED;
-  if (small_path(B, N, F, T, K, domain, source_model)) return SSSPY_ROUTE_LATENCY;
-  if (wide_basis_shape(N, K) && !(fast_path(N, F, T, K, domain, source_model) && K <= 32))
-    return SSSPY_ROUTE_WIDE_BASIS;
-  if (fast_path(N, F, T, K, domain, source_model)) return SSSPY_ROUTE_THROUGHPUT;
-  return SSSPY_ROUTE_GENERIC;
+  return p.summary;
 }
 
 size_t ssspy_fold_scalar_slots_workspace_bytes(long long total, int nslots) {
