@@ -91,8 +91,10 @@ const char *ssspy_amd_version(void);
  * 2: round 6 (ssspy_covariance_congruence_tracked added; round-5 signatures of
  *    ssspy_ilrma_loss_workspace_bytes / ssspy_fastmnmf_diagonalizer_covariance).
  * 3: round 6 (ssspy_ilrma_ip1_update_loss_slots: `logdet` became slots,
- *    ssspy_ilrma_deferred_logdet_slots added). */
-#define SSSPY_ABI_VERSION 4
+ *    ssspy_ilrma_deferred_logdet_slots added).
+ * 4: the ssspy_cacgmm_* entry points added.
+ * 5: ssspy_fastmnmf_route added (additive: no existing argument list changed). */
+#define SSSPY_ABI_VERSION 5
 int ssspy_abi_version(void);
 const char *ssspy_last_error(void);
 
@@ -746,6 +748,67 @@ int ssspy_fastmnmf_loss_data_handover_slots(const double *D, const double *basis
                                             const double *activation, const double *handover,
                                             double *slots, long long slot_stride, int B, int N,
                                             int M, int F, int T, int K, void *stream);
+
+/* Which kernels the FastGaussMNMF entry points take for a shape (host only, launches nothing; ABI
+ * version 5): for tests and tools that must know which launcher branch a case exercises.  A
+ * projection of the launch plan the entry points and launchers obey (csrc/mnmf_plan.hpp).  The value
+ * names the kernel family:
+ *   TILED    2..4 sources and channels (mnmf_kernels.hip)
+ *   GENERIC  up to 8 of either (fmnmf_generic.hip)
+ *   RUNTIME  9..16 of either (fmnmf_rt.hip)
+ * `handover`: whether the caller passes a hand-over buffer (ssspy_fastmnmf_update_handover).
+ * plan (may be NULL): SSSPY_MNMF_PLAN_INTS ints on the TILED family (0, and 0 0 1 0 for the frame
+ * splits, elsewhere), at the SSSPY_MNMF_PLAN_* indices:
+ *   FAST           basis, activation, covariance and spatial passes take the throughput form (0: the
+ *                  k_mnmf_*<M, KSMALL> kernels -- n_basis > 16, or SSSPY_AMD_NO_FAST in the environment)
+ *   KSMALL         n_basis <= 16 (the KSMALL = true instances of those kernels and of the loss)
+ *   BASIS_COPY     the basis pass writes scratch and the result is copied back (n_basis > 16)
+ *   GLDS_COV, GLDS_SPATIAL   the covariance / spatial pass takes the LDS-DMA form (whole frame tiles;
+ *                  the spatial pass only when it writes the hand-over), else the register-fed form
+ *   KQ             k-slabs of 4 of the throughput instances and of the closed-form Wiener filter:
+ *                  2 (n_basis <= 8), 4 (9..16), 0 (above)
+ *   HANDOVER       ssspy_fastmnmf_handover_doubles() > 0
+ *   TAIL_FULL, _TAIL, _SPLIT, _GROUPS      frame splits of the 256-slot passes (basis without
+ *                  hand-over, covariance, spatial): work items (mixture, 64-bin group) that walk all
+ *                  frames, items whose frames are split, frame chunks of a split item, bin groups
+ *   HTAIL_FULL, ...                        the same of the 512-slot hand-over basis and loss passes
+ *   ACT_CHUNKS     bin chunks the activation pass folds
+ *   IP1_RECORDS    the diagonaliser step hands IP1 the partial covariance records (every item split,
+ *                  latency form of IP1) instead of folding them
+ *   SPATIAL_FOLD_IN_NORM   with SSSPY_MNMF_SPATIAL | SSSPY_MNMF_NORMALIZE in one call the fold of
+ *                  the spatial pass is left to the normalisation (every item split)
+ *   LOSS_SLOTS     ssspy_fastmnmf_loss_handover_slots()
+ *   LOGDET_SLOTS   ssspy_fastmnmf_deferred_logdet_slots()
+ * Returns -1 for arguments the passes reject (a hand-over for a shape without one included). */
+enum {
+  SSSPY_MNMF_ROUTE_TILED = 0,
+  SSSPY_MNMF_ROUTE_GENERIC = 1,
+  SSSPY_MNMF_ROUTE_RUNTIME = 2,
+};
+enum {
+  SSSPY_MNMF_PLAN_FAST = 0,
+  SSSPY_MNMF_PLAN_KSMALL = 1,
+  SSSPY_MNMF_PLAN_BASIS_COPY = 2,
+  SSSPY_MNMF_PLAN_GLDS_COV = 3,
+  SSSPY_MNMF_PLAN_GLDS_SPATIAL = 4,
+  SSSPY_MNMF_PLAN_KQ = 5,
+  SSSPY_MNMF_PLAN_HANDOVER = 6,
+  SSSPY_MNMF_PLAN_TAIL_FULL = 7,
+  SSSPY_MNMF_PLAN_TAIL_TAIL = 8,
+  SSSPY_MNMF_PLAN_TAIL_SPLIT = 9,
+  SSSPY_MNMF_PLAN_TAIL_GROUPS = 10,
+  SSSPY_MNMF_PLAN_HTAIL_FULL = 11,
+  SSSPY_MNMF_PLAN_HTAIL_TAIL = 12,
+  SSSPY_MNMF_PLAN_HTAIL_SPLIT = 13,
+  SSSPY_MNMF_PLAN_HTAIL_GROUPS = 14,
+  SSSPY_MNMF_PLAN_ACT_CHUNKS = 15,
+  SSSPY_MNMF_PLAN_IP1_RECORDS = 16,
+  SSSPY_MNMF_PLAN_SPATIAL_FOLD_IN_NORM = 17,
+  SSSPY_MNMF_PLAN_LOSS_SLOTS = 18,
+  SSSPY_MNMF_PLAN_LOGDET_SLOTS = 19,
+  SSSPY_MNMF_PLAN_INTS = 20,
+};
+int ssspy_fastmnmf_route(int B, int N, int M, int F, int T, int K, int handover, int *plan);
 
 /* U[b,i,m] = (1/T) sum_j x x^H / R~_ijm  -> (B,F,M,M,M): the covariances the diagonaliser update
  * (IP1 inside ssspy_fastmnmf_update, or ssspy_update_by_ip2 for diagonalizer_algorithm="IP2") needs.

@@ -23,13 +23,19 @@ CONTRAST_LAPLACE, CONTRAST_GAUSS, CONTRAST_GAUSS_FIXED = 0, 1, 2
 # SSSPY_ROUTE_*: what ssspy_ilrma_route returns
 (ROUTE_LATENCY, ROUTE_THROUGHPUT, ROUTE_GROUPED, ROUTE_GENERIC, ROUTE_WIDE_BASIS,
  ROUTE_RUNTIME_N) = range(6)
+# SSSPY_MNMF_ROUTE_*: what ssspy_fastmnmf_route returns; SSSPY_MNMF_PLAN_*: the names of its plan ints
+MNMF_ROUTE_TILED, MNMF_ROUTE_GENERIC, MNMF_ROUTE_RUNTIME = range(3)
+MNMF_PLAN_FIELDS = ("fast", "ksmall", "basis_copy", "glds_cov", "glds_spatial", "kq", "handover",
+                    "tail_full", "tail_tail", "tail_split", "tail_groups", "htail_full", "htail_tail",
+                    "htail_split", "htail_groups", "act_chunks", "ip1_records", "spatial_fold_in_norm",
+                    "loss_slots", "logdet_slots")
 MAX_PAIRS = 32
 # SSSPY_MAX_SOURCES (per-N kernels: IPA, both MNMF classes, the Hermitian operators; GaussMNMF's
 # channels and the ILRMA partition entry points stop there), SSSPY_RT_MAX_SOURCES (run-time-N kernels:
 # the shared operators, ILRMA, AuxIVA, FastGaussMNMF's channels and sources, GaussMNMF's sources),
 # SSSPY_MAX_BASIS
 MAX_SOURCES, RT_MAX_SOURCES, MAX_BASIS = 8, 16, 65536
-ABI_VERSION = 4  # SSSPY_ABI_VERSION of the include/ssspy_amd.h these prototypes mirror
+ABI_VERSION = 5  # SSSPY_ABI_VERSION of the include/ssspy_amd.h these prototypes mirror
 
 _p, _i, _d, _z = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_size_t
 _q = ctypes.c_longlong
@@ -149,6 +155,7 @@ PROTOTYPES = {
     "ssspy_fastmnmf_update_handover_logdet": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i,
                                                    _i, _d, _p, _z, _p, _p, _p, _p, _q, _p]),
     "ssspy_fastmnmf_loss_handover_slots": (_i, [_i, _i, _i, _i, _i, _i]),
+    "ssspy_fastmnmf_route": (_i, [_i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]),
     "ssspy_fastmnmf_loss_data_handover_slots": (_i, [_p, _p, _p, _p, _p, _q, _i, _i, _i, _i, _i, _i,
                                                      _p]),
     "ssspy_fastmnmf_loss_data_handover": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _z,

@@ -727,6 +727,19 @@ def fastmnmf_workspace(B, N, M, F, T, K, dev):
     return _workspace(_L().ssspy_fastmnmf_workspace_bytes(B, N, M, F, T, K), dev)
 
 
+def fastmnmf_route(B, N, M, F, T, K, handover=False):
+    """(route, plan): the _lib.MNMF_ROUTE_* kernel family of the FastGaussMNMF entry points for this
+    shape and, for the tiled family, what its launchers decide, as a dict over
+    _lib.MNMF_PLAN_FIELDS (see ssspy_fastmnmf_route in the header).  Host only."""
+    import ctypes
+
+    plan = (ctypes.c_int * len(_lib.MNMF_PLAN_FIELDS))()
+    route = int(_L().ssspy_fastmnmf_route(B, N, M, F, T, K, 1 if handover else 0, plan))
+    if route < 0:
+        raise ValueError("fastmnmf_route: bad shape")
+    return route, dict(zip(_lib.MNMF_PLAN_FIELDS, (int(v) for v in plan)))
+
+
 def fastmnmf_update(X, C, Q, D, basis, activation, steps, flooring, ws, ws_bytes, info):
     B, M, F, T = X.shape
     N, K = basis.shape[1], basis.shape[-1]

@@ -1,14 +1,13 @@
 // C-ABI entry points of the FastGaussMNMF path (kernels: mnmf_kernels.hip, one unit per N).
 #include "common.hpp"
+#include "mnmf_plan.hpp"
 
 namespace ssspy {
 
 #define DECL_N(n)                                                                                \
-  int mnmf_handover_ok_n##n(int, int, int, int);                                                \
   int mnmf_loss_handover_n##n(const double *, const double *, const double *, const double *,   \
                               const double *, double *, void *, int, int, int, int, int,        \
                               hipStream_t);                                                     \
-  int mnmf_loss_handover_slots_n##n(int, int, int);                                             \
   int mnmf_loss_handover_raw_n##n(const double *, const double *, const double *, const double *, \
                                   const double *, double *, long long, int, int, int, int, int, \
                                   hipStream_t);                                                 \
@@ -47,7 +46,6 @@ DECL_N(2) DECL_N(3) DECL_N(4)
 int ip1_with_power(void *W, const void *U, const void *C, double *qbuf, int B, int F, int N,
                    int floor_kind, double floor_eps, int *info, hipStream_t st);
 int row_power(const void *W, const void *C, double *qbuf, int B, int F, int N, hipStream_t st);
-bool ip1_small_shape(int B, int F, int N);
 int ip1_from_records(void *W, const void *records, int nchunks, int rbins, long long rec_stride,
                      const void *C, double *qbuf, int B, int F, int N, int floor_kind,
                      double floor_eps, int *info, hipStream_t st, double *logdet,
@@ -75,25 +73,11 @@ int fmnmf_generic_separate_eig(const void *X, const void *Q, void *Qinv, const d
                                int M, int F, int T, int K, int ref, int stage, double *lam,
                                void *P, int *info, hipStream_t st);
 // M or N in 9..16: the run-time forms of fmnmf_rt.hip
-bool fmnmf_rt_shape(int N, int M);
 int fmnmf_rt_diagonalizer_covariance(const void *X, const double *D, const double *basis,
                                      const double *act, void *U, int B, int N, int M, int F, int T,
                                      int K, hipStream_t st);
 
-// the MFMA-tile kernels (mnmf_kernels.hip) are compiled for 2..4 sources and channels
-static inline bool mnmf_tiled(int N, int M) { return N >= 2 && N <= 4 && M >= 2 && M <= 4; }
-
 static inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
-static inline int mnmf_chunks(int B, int F, int T, int K) {
-  const long long blocks0 = (long long)B * ((T + 63) / 64) * ((K + 15) / 16);
-  const int ntiles = (F + 15) / 16;
-  long long want = (512 + blocks0 - 1) / blocks0;
-  if (want < 1) want = 1;
-  if (want > 16) want = 16;
-  if (want > ntiles) want = ntiles;
-  return (int)want;
-}
 
 struct MnmfWs {
   size_t part, btmp, U, qbuf, qinv, tail, generic, total;
@@ -151,9 +135,9 @@ __global__ __launch_bounds__(256) void k_mnmf_activation_finalize(double *act,
 // P / pscale: the |Q x|^2 hand-over (nullptr: the pass reads x and Q)
 static int step_basis(const void *X, const void *Q, const double *D, double *basis,
                       const double *act, int B, int N, int M, int F, int T, int K, int fk,
-                      double eps, char *ws, const MnmfWs &w, const double *P,
+                      double eps, char *ws, const MnmfWs &w, const MnmfPlan &plan, const double *P,
                       const double *pscale, hipStream_t st) {
-  double *out = K > 16 ? (double *)(ws + w.btmp) : basis;
+  double *out = plan.basis_via_copy ? (double *)(ws + w.btmp) : basis;
   auto run = [&]() -> int {
     MNMF_DISPATCH(N, mnmf_basis, X, Q, D, basis, out, act, B, M, F, T, K, fk, eps,
                   (double *)(ws + w.tail), P, pscale, st);
@@ -170,9 +154,9 @@ static int step_basis(const void *X, const void *Q, const double *D, double *bas
 
 static int step_activation(const void *X, const void *Q, const double *D, const double *basis,
                            double *act, int B, int N, int M, int F, int T, int K, int fk,
-                           double eps, char *ws, const MnmfWs &w, const double *P,
-                           const double *pscale, hipStream_t st) {
-  const int chunks = mnmf_chunks(B, F, T, K);
+                           double eps, char *ws, const MnmfWs &w, const MnmfPlan &plan,
+                           const double *P, const double *pscale, hipStream_t st) {
+  const int chunks = plan.act_chunks;
   double *part = (double *)(ws + w.part);
   auto run = [&]() -> int {
     MNMF_DISPATCH(N, mnmf_activation, X, Q, D, basis, act, part, chunks, B, M, F, T, K, P, pscale,
@@ -187,8 +171,7 @@ static int step_activation(const void *X, const void *Q, const double *D, const 
 }
 
 static int handover_ok(int B, int N, int M, int F, int T, int K) {
-  if (!mnmf_tiled(N, M)) return 0;
-  MNMF_DISPATCH(N, mnmf_handover_ok, B, F, T, K);
+  return make_mnmf_plan(B, N, M, F, T, K).handover ? 1 : 0;
 }
 static int handover_fill(const void *X, const void *Q, double *P, double *pscale, int B, int N,
                          int M, int F, int T, hipStream_t st) {
@@ -210,6 +193,7 @@ static int fastmnmf_update_impl(const void *X, const void *C, void *Q, double *D
   SSSPY_REQUIRE(X && Q && D && basis && activation && B > 0 && F > 0 && T > 0,
                 "fastmnmf_update: bad argument");
   SSSPY_REQUIRE(K >= 1 && K <= SSSPY_MAX_BASIS, "fastmnmf_update: n_basis must be in [1, 65536]");
+  const MnmfPlan plan = make_mnmf_plan(B, N, M, F, T, K);  // once per call; the steps below read it
   const MnmfWs w = mnmf_ws(B, N, M, F, T, K);
   SSSPY_REQUIRE(workspace && workspace_bytes >= w.total, "fastmnmf_update: workspace too small");
   SSSPY_REQUIRE(!(steps & SSSPY_MNMF_NORMALIZE) || C, "fastmnmf_update: normalisation needs C");
@@ -218,7 +202,7 @@ static int fastmnmf_update_impl(const void *X, const void *C, void *Q, double *D
   if (logdet) {
     SSSPY_REQUIRE(steps & SSSPY_MNMF_DIAGONALIZER, "fastmnmf_update: logdet without the IP1 step");
   }
-  if (!mnmf_tiled(N, M)) {
+  if (plan.family != MnmfFamily::Tiled) {
     SSSPY_REQUIRE(!handover, "fastmnmf_update: no hand-over for this shape");
     if (logdet) {
       rc = ssspy_sum_logdet(Q, logdet, B, F, M, (void *)st);
@@ -231,7 +215,7 @@ static int fastmnmf_update_impl(const void *X, const void *C, void *Q, double *D
   double *P = handover, *pscale = handover ? handover + (size_t)B * M * F * T : nullptr;
   if (handover) {
     SSSPY_REQUIRE(valid, "fastmnmf_update: hand-over without its validity flag");
-    SSSPY_REQUIRE(handover_ok(B, N, M, F, T, K) == 1, "fastmnmf_update: no hand-over for this shape");
+    SSSPY_REQUIRE(plan.handover, "fastmnmf_update: no hand-over for this shape");
   }
   bool have_p = handover && *valid;
   if (handover && !have_p && (steps & (SSSPY_MNMF_BASIS | SSSPY_MNMF_ACTIVATION))) {
@@ -242,12 +226,12 @@ static int fastmnmf_update_impl(const void *X, const void *C, void *Q, double *D
   if (valid) *valid = 0;  // until the call is through
   if (steps & SSSPY_MNMF_BASIS) {
     rc = step_basis(X, Q, D, basis, activation, B, N, M, F, T, K, floor_kind, floor_eps, ws, w,
-                    have_p ? P : nullptr, pscale, st);
+                    plan, have_p ? P : nullptr, pscale, st);
     if (rc) return rc;
   }
   if (steps & SSSPY_MNMF_ACTIVATION) {
     rc = step_activation(X, Q, D, basis, activation, B, N, M, F, T, K, floor_kind, floor_eps, ws, w,
-                         have_p ? P : nullptr, pscale, st);
+                         plan, have_p ? P : nullptr, pscale, st);
     if (rc) return rc;
   }
   double *qbuf = (double *)(ws + w.qbuf);
@@ -258,7 +242,7 @@ static int fastmnmf_update_impl(const void *X, const void *C, void *Q, double *D
     // partial records itself (no fold kernel, U is not materialised)
     int split = 0;
     long long rec = 0;
-    const bool small = ip1_small_shape(B, F, M);
+    const bool small = plan.ip1_small;
     auto run = [&]() -> int {
       MNMF_DISPATCH(N, mnmf_wcov, X, D, basis, activation, U, B, M, F, T, K,
                     (double *)(ws + w.tail), small ? &split : nullptr, &rec, st);
@@ -350,7 +334,7 @@ int ssspy_fastmnmf_update_handover(const void *X, const void *C, void *Q, double
 
 int ssspy_fastmnmf_deferred_logdet_slots(int B, int N, int M, int F, int T, int K) {
   if (B <= 0 || N <= 0 || M <= 0 || F <= 0 || T <= 0 || K <= 0) return 0;
-  return (mnmf_tiled(N, M) && ip1_small_shape(B, F, M)) ? (F + 15) / 16 : 1;
+  return make_mnmf_plan(B, N, M, F, T, K).logdet_slots;
 }
 
 int ssspy_fastmnmf_update_handover_logdet(const void *X, const void *C, void *Q, double *D,
@@ -378,10 +362,11 @@ int ssspy_fastmnmf_diagonalizer_covariance(const void *X, const double *D, const
     return fail(SSSPY_ERR_UNSUPPORTED,
                 "fastmnmf_diagonalizer_covariance: n_sources and n_channels must be at most 16");
   // 9..16 channels or sources: the fused pass of fmnmf_rt.hip (weights formed inside; no workspace)
-  if (fmnmf_rt_shape(N, M))
+  const MnmfFamily family = make_mnmf_plan(B, N, M, F, T, K).family;
+  if (family == MnmfFamily::Runtime)
     return fmnmf_rt_diagonalizer_covariance(X, D, basis, activation, U, B, N, M, F, T, K,
                                             as_stream(stream));
-  if (!mnmf_tiled(N, M))
+  if (family != MnmfFamily::Tiled)
     return fail(SSSPY_ERR_UNSUPPORTED,
                 "fastmnmf_diagonalizer_covariance: beyond 4 sources / channels use "
                 "ssspy_fastmnmf_weights + ssspy_weighted_covariance");
@@ -433,7 +418,7 @@ int ssspy_fastmnmf_loss_data(const void *X, const void *Q, const double *D, cons
   SSSPY_REQUIRE(workspace && workspace_bytes >= fastmnmf_loss_ws(B, N, M, F, T),
                 "fastmnmf_loss_data: workspace too small (ssspy_fastmnmf_loss_workspace_bytes)");
   hipStream_t st = as_stream(stream);
-  if (!mnmf_tiled(N, M))
+  if (make_mnmf_plan(B, N, M, F, T, K).family != MnmfFamily::Tiled)
     return fmnmf_generic_loss(X, Q, D, basis, activation, out, workspace, B, N, M, F, T, K, st);
   MNMF_DISPATCH(N, mnmf_loss, X, Q, D, basis, activation, out, workspace, B, M, F, T, K, st);
 }
@@ -458,8 +443,24 @@ int ssspy_fastmnmf_loss_data_handover(const double *D, const double *basis,
 
 int ssspy_fastmnmf_loss_handover_slots(int B, int N, int M, int F, int T, int K) {
   if (B <= 0 || N <= 0 || M <= 0 || F <= 0 || T <= 0 || K <= 0) return 0;
-  if (handover_ok(B, N, M, F, T, K) != 1) return 0;
-  MNMF_DISPATCH(N, mnmf_loss_handover_slots, B, F, T);
+  return make_mnmf_plan(B, N, M, F, T, K).loss_slots;
+}
+
+int ssspy_fastmnmf_route(int B, int N, int M, int F, int T, int K, int handover, int *plan) {
+  if (B <= 0 || F <= 0 || T <= 0 || K < 1 || K > SSSPY_MAX_BASIS) return -1;
+  const MnmfPlan p = make_mnmf_plan(B, N, M, F, T, K);
+  if (p.family == MnmfFamily::None) return -1;
+  if (handover && !p.handover) return -1;  // the update rejects the buffer for such a shape
+  if (plan) {
+    const bool h = handover != 0;
+    const TailPlan &t = p.tail, &th = p.tail_handover;
+    const int v[SSSPY_MNMF_PLAN_INTS] = {
+        p.fast, p.ksmall, p.basis_via_copy, p.glds, h && p.glds, p.kq, p.handover,
+        t.full, t.tail, t.split, t.groups, th.full, th.tail, th.split, th.groups,
+        p.act_chunks, p.ip1_small && p.all_split, p.all_split, p.loss_slots, p.logdet_slots};
+    for (int e = 0; e < SSSPY_MNMF_PLAN_INTS; ++e) plan[e] = v[e];
+  }
+  return (int)p.family;
 }
 
 int ssspy_fastmnmf_loss_data_handover_slots(const double *D, const double *basis,
@@ -485,7 +486,7 @@ int ssspy_fastmnmf_separate(const void *X, const void *Q, const double *D, const
   const MnmfWs w = mnmf_ws(B, N, M, F, T, K);
   SSSPY_REQUIRE(workspace && workspace_bytes >= w.total, "fastmnmf_separate: workspace too small");
   void *Qinv = (char *)workspace + w.qinv;
-  if (!mnmf_tiled(N, M))
+  if (make_mnmf_plan(B, N, M, F, T, K).family != MnmfFamily::Tiled)
     return fmnmf_generic_separate(X, Q, Qinv, D, basis, activation, Y, B, N, M, F, T, K,
                                   reference_id, floor_kind, floor_eps, info,
                                   (int *)((char *)workspace + w.qbuf), as_stream(stream));

@@ -17,6 +17,7 @@
 #include "hermitian.hpp"
 #include "nmf_tile.hpp"
 #include "smallmat.hpp"
+#include "mnmf_plan.hpp"
 #include "tail_plan.hpp"
 
 #ifndef SSSPY_N
@@ -621,10 +622,7 @@ struct LogSumM {
 };
 // the |Q x|^2 hand-over: none, read it instead of x (basis pass), write it (spatial pass)
 enum { P_NONE = 0, P_READ = 1, P_WRITE = 2 };
-#ifndef SSSPY_MNMF_PBASIS_WAVES
-#define SSSPY_MNMF_PBASIS_WAVES 2
-#endif
-constexpr int PBASIS_WAVES = SSSPY_MNMF_PBASIS_WAVES;  // waves per SIMD of the P_READ basis pass
+// (PBASIS_WAVES, the waves per SIMD of the P_READ basis pass: mnmf_plan.hpp)
 
 // grid: 1-D, see TailPlan (tail_plan.hpp): a work item is (mixture, 64-bin group), wave w owns bins
 // [64 group + 16 w, +16).  Unsplit items finish their bins in place; the split items of the last
@@ -2158,31 +2156,10 @@ constexpr int cov_lds_mm() {
   return cov_lds_doubles_per_wave<M, M>();
 }
 
-// The bin-split variants run on the two-level schedule of tail_plan.hpp: whole rounds of 512
-// workgroups unsplit, the remainder (or a small batch) split along the frames.
-static inline bool mnmf_fast_ok(int B, int F, int T, int K) {
-  static const bool disabled = std::getenv("SSSPY_AMD_NO_FAST") != nullptr;
-  // one mixture must fit a 32-bit buffer descriptor (up to 4 channels of complex128)
-  return !disabled && K <= 16 && (long long)4 * F * T * 16 < (1ll << 32);
-}
-static inline TailPlan mnmf_plan(int B, int F, int T) {
-  // these kernels hold one workgroup per CU (x prefetch in registers, > 256 VGPR + AGPR)
-  return make_tail_plan(B, (F + 63) / 64, (T + 15) / 16, 256);
-}
-// private activation tiles per wave (n_basis <= 8; the barrier-free form of k_mnmf_binmajor_glds)
-// Measured (benchmarks/tools/mnmf_steps.py, configs[3] shape): the covariance pass gains at every
-// batch (32 mixtures: 267 -> 253 us, 128: 964 -> 908); the spatial pass, bound by its read + write
-// stream, does not (401 -> 400, 1259 -> 1309) -- so only the covariance pass takes it.  (The A / B
-// switches of round 5 -- private tiles in both passes, |Q x|^2 stores transposed through LDS,
-// register-fed passes at tile-aligned frame counts -- went in round 6 with their instantiations.)
-// the LDS-DMA form of the two x-reading passes (k_mnmf_binmajor_glds): whole tiles of frames
-static inline bool mnmf_glds_ok(int B, int F, int T, int K) {
-  return mnmf_fast_ok(B, F, T, K) && T % 16 == 0;
-}
-
-// whether the |Q x|^2 hand-over (P, pscale) is taken by the passes of this shape
-int LAUNCHER(mnmf_handover_ok)(int B, int F, int T, int K) {
-  return (mnmf_fast_ok(B, F, T, K) && T % 2 == 0) ? 1 : 0;
+// Which form each pass takes is decided by make_mnmf_plan() (mnmf_plan.hpp); the launchers below only
+// read it.  N is this unit's source count.
+static inline MnmfPlan unit_plan(int B, int M, int F, int T, int K) {
+  return make_mnmf_plan(B, N, M, F, T, K);
 }
 
 int LAUNCHER(mnmf_qx2)(const void *X, const void *Q, double *P, double *pscale, int B, int M,
@@ -2198,13 +2175,13 @@ int LAUNCHER(mnmf_basis)(const void *X, const void *Q, const double *Dsp, const 
                          int floor_kind, double eps, double *tailpart, const double *P,
                          const double *pscale, hipStream_t st) {
   Dims d{B, F, T, K};
-  if (mnmf_fast_ok(B, F, T, K) && basis_out == basis) {
+  const MnmfPlan mp = unit_plan(B, M, F, T, K);
+  if (mp.fast && basis_out == basis) {
     // two workgroups per CU with the hand-over (no x tiles, no Q in registers)
-    const TailPlan plan = P ? make_tail_plan(B, (F + 63) / 64, (T + 15) / 16, 256 * PBASIS_WAVES)
-                            : mnmf_plan(B, F, T);
+    const TailPlan plan = P ? mp.tail_handover : mp.tail;
     dim3 fgrid(plan.full + plan.tail * plan.split);
     MNMF_DISPATCH_M(M, {
-      if (P && K <= 8)
+      if (P && mp.kq == 2)
         hipLaunchKernelGGL((k_mnmf_binmajor_fast<MM, MODE_BASIS, P_READ, 2>), fgrid, dim3(256), 0,
                            st, (const c128 *)X, (const c128 *)Q, (double *)Dsp, basis_out, act,
                            (c128 *)nullptr, F, T, K, floor_kind, eps, plan, tailpart,
@@ -2228,7 +2205,7 @@ int LAUNCHER(mnmf_basis)(const void *X, const void *Q, const double *Dsp, const 
   dim3 grid((F + 15) / 16, kt_count(K), B), block(256);
   const size_t lds = (size_t)4 * N * 2 * 256 * sizeof(double);
   MNMF_DISPATCH_M(M, {
-    if (K <= 16)
+    if (mp.ksmall)
       hipLaunchKernelGGL((k_mnmf_basis<MM, true>), grid, block, lds, st, (const c128 *)X,
                          (const c128 *)Q, Dsp, basis, basis_out, act, d, floor_kind, eps);
     else
@@ -2247,7 +2224,8 @@ int LAUNCHER(mnmf_activation)(const void *X, const void *Q, const double *Dsp, c
   const int tiles_per_chunk = (ntiles + nchunks - 1) / nchunks;
   const int ktiles = kt_count(K);
   dim3 grid((T + 63) / 64, nchunks, B * ktiles), block(256);
-  if (mnmf_fast_ok(B, F, T, K)) {
+  const MnmfPlan mp = unit_plan(B, M, F, T, K);
+  if (mp.fast) {
     MNMF_DISPATCH_M(M, {
       if (P)
         hipLaunchKernelGGL((k_mnmf_activation_fast<MM, true>), grid, block, 0, st, (const c128 *)X,
@@ -2262,7 +2240,7 @@ int LAUNCHER(mnmf_activation)(const void *X, const void *Q, const double *Dsp, c
     return check_launch("k_mnmf_activation_fast");
   }
   MNMF_DISPATCH_M(M, {
-    if (K <= 16)
+    if (mp.ksmall)
       hipLaunchKernelGGL((k_mnmf_activation<MM, true>), grid, block, 0, st, (const c128 *)X,
                          (const c128 *)Q, Dsp, basis, act, part, d, ktiles, tiles_per_chunk,
                          nchunks);
@@ -2283,13 +2261,14 @@ int LAUNCHER(mnmf_wcov)(const void *X, const double *Dsp, const double *basis, c
                         int *split_out, long long *rec_out, hipStream_t st) {
   Dims d{B, F, T, K};
   if (split_out) *split_out = 0;
-  if (mnmf_fast_ok(B, F, T, K) && tailpart) {
-    const TailPlan plan = mnmf_plan(B, F, T);
+  const MnmfPlan mp = unit_plan(B, M, F, T, K);
+  if (mp.fast && tailpart) {
+    const TailPlan plan = mp.tail;
     dim3 fgrid(plan.full + plan.tail * plan.split);
-    const bool records = split_out && rec_out && plan.full == 0 && plan.tail > 0;
-    const bool glds = mnmf_glds_ok(B, F, T, K);
+    const bool records = split_out && rec_out && mp.all_split;
+    const bool glds = mp.glds;
     MNMF_DISPATCH_M(M, {
-      if (glds && K <= 8)
+      if (glds && mp.kq == 2)
         hipLaunchKernelGGL((k_mnmf_binmajor_glds<MM, MODE_WCOV, 2, true>), fgrid, dim3(256), 0, st,
                            (const c128 *)X, (const c128 *)nullptr, (double *)Dsp, basis, act,
                            (c128 *)U, F, T, K, plan, tailpart, (double *)nullptr);
@@ -2315,7 +2294,7 @@ int LAUNCHER(mnmf_wcov)(const void *X, const double *Dsp, const double *basis, c
   dim3 grid((F + 15) / 16, 1, B), block(256);
   MNMF_DISPATCH_M(M, {
     const size_t lds = (size_t)4 * cov_lds_mm<MM>() * sizeof(double);
-    if (K <= 16)
+    if (mp.ksmall)
       hipLaunchKernelGGL((k_mnmf_wcov<MM, true>), grid, block, lds, st, (const c128 *)X, Dsp, basis,
                          act, (c128 *)U, d);
     else
@@ -2337,15 +2316,16 @@ int LAUNCHER(mnmf_spatial)(const void *X, const void *Q, double *Dsp, const doub
                            hipStream_t st) {
   if (split_out) *split_out = 0;
   Dims d{B, F, T, K};
-  if (mnmf_fast_ok(B, F, T, K)) {
-    const TailPlan plan = mnmf_plan(B, F, T);
+  const MnmfPlan mp = unit_plan(B, M, F, T, K);
+  if (mp.fast) {
+    const TailPlan plan = mp.tail;
     dim3 fgrid(plan.full + plan.tail * plan.split);
     if (P && !scale_follows)
       hipLaunchKernelGGL(k_mnmf_fill_ones, dim3((B * M + 255) / 256), dim3(256), 0, st, pscale,
                          B * M);
-    const bool glds = P && mnmf_glds_ok(B, F, T, K);
+    const bool glds = P && mp.glds;
     MNMF_DISPATCH_M(M, {
-      if (glds && K <= 8)
+      if (glds && mp.kq == 2)
         hipLaunchKernelGGL((k_mnmf_binmajor_glds<MM, MODE_SPATIAL, 2>), fgrid, dim3(256), 0, st,
                            (const c128 *)X, (const c128 *)Q, Dsp, basis, act, (c128 *)nullptr, F,
                            T, K, plan, tailpart, P);
@@ -2363,7 +2343,7 @@ int LAUNCHER(mnmf_spatial)(const void *X, const void *Q, double *Dsp, const doub
                          (const c128 *)X, (const c128 *)Q, Dsp, (double *)basis, act,
                          (c128 *)nullptr, F, T, K, 0, 0.0, plan, tailpart, (double *)nullptr,
                          (const double *)nullptr);
-      if (split_out && plan.full == 0 && plan.tail > 0)
+      if (split_out && mp.all_split)
         *split_out = plan.split;
       else if (plan.tail > 0)
         hipLaunchKernelGGL((k_mnmf_spatial_finalize<MM>), dim3((64 * N * MM + 255) / 256, plan.tail),
@@ -2374,7 +2354,7 @@ int LAUNCHER(mnmf_spatial)(const void *X, const void *Q, double *Dsp, const doub
   dim3 grid((F + 15) / 16, 1, B), block(256);
   MNMF_DISPATCH_M(M, {
     const size_t lds = (size_t)4 * 2 * N * MM * 16 * sizeof(double);
-    if (K <= 16)
+    if (mp.ksmall)
       hipLaunchKernelGGL((k_mnmf_spatial<MM, true>), grid, block, lds, st, (const c128 *)X,
                          (const c128 *)Q, Dsp, basis, act, d);
     else
@@ -2397,8 +2377,9 @@ int LAUNCHER(mnmf_loss)(const void *X, const void *Q, const double *Dsp, const d
   Dims d{B, F, T, K};
   dim3 grid((F + 15) / 16, 1, B), block(256);
   // (every block writes its slot: no reset needed)
+  const MnmfPlan mp = unit_plan(B, M, F, T, K);
   MNMF_DISPATCH_M(M, {
-    if (K <= 16)
+    if (mp.ksmall)
       hipLaunchKernelGGL((k_mnmf_loss<MM, true>), grid, block, 0, st, (const c128 *)X,
                          (const c128 *)Q, Dsp, basis, act, (double *)loss_ws, d);
     else
@@ -2413,11 +2394,12 @@ int LAUNCHER(mnmf_loss)(const void *X, const void *Q, const double *Dsp, const d
 int LAUNCHER(mnmf_loss_handover)(const double *Dsp, const double *basis, const double *act,
                                  const double *P, const double *pscale, double *out, void *loss_ws,
                                  int B, int M, int F, int T, int K, hipStream_t st) {
-  if (!mnmf_fast_ok(B, F, T, K) || T % 2 != 0)
+  const MnmfPlan mp = unit_plan(B, M, F, T, K);
+  if (!mp.handover)
     return fail(SSSPY_ERR_UNSUPPORTED, "fastmnmf_loss_data_handover: no hand-over for this shape");
-  const TailPlan plan = make_tail_plan(B, (F + 63) / 64, (T + 15) / 16, 256 * PBASIS_WAVES);
+  const TailPlan plan = mp.tail_handover;
   dim3 fgrid(plan.full + plan.tail * plan.split);
-  const int nslots = plan.groups * (plan.split > 1 ? plan.split : 1) * 4;
+  const int nslots = mp.loss_slots;
   int rc = scalar_slots_begin(loss_ws, B, nslots, st);
   if (rc) return rc;
   // (MODE_LOSS: `tailpart` = the slots, `floor_kind` = B, see the kernel)
@@ -2433,17 +2415,14 @@ int LAUNCHER(mnmf_loss_handover)(const double *Dsp, const double *basis, const d
 // The same with the per-wave shares left RAW in the caller's array, share s of mixture b at
 // slots[s * stride + b] (s < mnmf_loss_handover_slots): a record_loss run zeroes one array for all
 // its iterations and folds it once, instead of two memsets and a fold launch per loss.
-int LAUNCHER(mnmf_loss_handover_slots)(int B, int F, int T) {
-  const TailPlan plan = make_tail_plan(B, (F + 63) / 64, (T + 15) / 16, 256 * PBASIS_WAVES);
-  return plan.groups * (plan.split > 1 ? plan.split : 1) * 4;
-}
 int LAUNCHER(mnmf_loss_handover_raw)(const double *Dsp, const double *basis, const double *act,
                                      const double *P, const double *pscale, double *slots,
                                      long long stride, int B, int M, int F, int T, int K,
                                      hipStream_t st) {
-  if (!mnmf_fast_ok(B, F, T, K) || T % 2 != 0)
+  const MnmfPlan mp = unit_plan(B, M, F, T, K);
+  if (!mp.handover)
     return fail(SSSPY_ERR_UNSUPPORTED, "fastmnmf_loss_data_handover: no hand-over for this shape");
-  const TailPlan plan = make_tail_plan(B, (F + 63) / 64, (T + 15) / 16, 256 * PBASIS_WAVES);
+  const TailPlan plan = mp.tail_handover;
   dim3 fgrid(plan.full + plan.tail * plan.split);
   // (MODE_LOSS: `tailpart` = the slots, `floor_kind` = their stride, see the kernel)
   MNMF_DISPATCH_M(M, hipLaunchKernelGGL((k_mnmf_binmajor_fast<MM, MODE_LOSS, P_READ>), fgrid,
@@ -2478,12 +2457,13 @@ int LAUNCHER(mnmf_separate)(const void *X, const void *Q, void *Qinv, const doub
   MNMF_DISPATCH_M(M, {
     hipLaunchKernelGGL((k_mnmf_qinv<MM>), dim3((unsigned)((nbins + 63) / 64)), dim3(64), 0, st,
                        (const c128 *)Q, (c128 *)Qinv, nbins, info);
-    if (K <= 8 && floor_kind != SSSPY_FLOOR_ADD)
+    const int kq = unit_plan(B, M, F, T, K).kq;
+    if (kq == 2 && floor_kind != SSSPY_FLOOR_ADD)
       hipLaunchKernelGGL((k_mnmf_separate_closed_rows<MM, 8>),
                          dim3((F + SEP_BINS - 1) / SEP_BINS, (T + 255) / 256, B), dim3(256), 0, st,
                          (const c128 *)X, (const c128 *)Q, (const c128 *)Qinv, Dsp, basis, act,
                          (c128 *)Y, d, ref, eps, redo);
-    else if (K <= 16 && floor_kind != SSSPY_FLOOR_ADD)
+    else if (kq == 4 && floor_kind != SSSPY_FLOOR_ADD)
       hipLaunchKernelGGL((k_mnmf_separate_closed_rows<MM, 16>),
                          dim3((F + SEP_BINS - 1) / SEP_BINS, (T + 255) / 256, B), dim3(256), 0, st,
                          (const c128 *)X, (const c128 *)Q, (const c128 *)Qinv, Dsp, basis, act,
