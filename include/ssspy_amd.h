@@ -78,7 +78,8 @@ enum { SSSPY_SOURCE_ME = 0x100 };
  * (partitioning=True) stay at SSSPY_MAX_SOURCES (SSSPY_ERR_UNSUPPORTED above). */
 #define SSSPY_RT_MAX_SOURCES 16
 /* n_basis: the kernels walk any number of bases (dense products above 32; checked against the
- * oracle at 1500 and 3000); the bound only keeps 32-bit index arithmetic safe.  Up to round 5: 1024. */
+ * oracle at 1500 and 3000); the bound only keeps 32-bit index arithmetic safe.  Up to round 5: 1024.
+ * The ssspy_gmnmf_* entry points are bounded further by a workgroup's LDS (see there). */
 #define SSSPY_MAX_BASIS 65536
 #define SSSPY_MAX_PARTITION_BASIS 1024 /* partitioning=True: the latent update keeps N x n_basis in LDS */
 #define SSSPY_MAX_PAIRS 128 /* every pair of 16 sources: 120 */
@@ -93,8 +94,9 @@ const char *ssspy_amd_version(void);
  * 3: round 6 (ssspy_ilrma_ip1_update_loss_slots: `logdet` became slots,
  *    ssspy_ilrma_deferred_logdet_slots added).
  * 4: the ssspy_cacgmm_* entry points added.
- * 5: ssspy_fastmnmf_route added (additive: no existing argument list changed). */
-#define SSSPY_ABI_VERSION 5
+ * 5: ssspy_fastmnmf_route added (additive: no existing argument list changed).
+ * 6: ssspy_gmnmf_route added (additive). */
+#define SSSPY_ABI_VERSION 6
 int ssspy_abi_version(void);
 const char *ssspy_last_error(void);
 
@@ -860,9 +862,14 @@ int ssspy_fastmnmf_separate_eig(const void *X, const void *Q, const double *D, c
 /* ------------------------------------------------------------------ GaussMNMF (full-rank SCM)
  * State: basis (B,N,F,K) f64, activation (B,N,K,T) f64, spatial (B,N,F,M,M) c128 Hermitian PSD
  * (the reference's `spatial` (N,F,M,M) with a batch axis).  n_sources N in [1, 16] (above 8 the
- * per-point kernels run their 16-source instantiations; SSSPY_ERR_UNSUPPORTED above 16, and above 8
- * sources also when the bin's spatial matrices and basis rows overflow a workgroup's 160 KB of LDS:
- * n_basis beyond ~600 at 8 channels).  n_channels M in [2, 8]: one lane per
+ * per-point kernels run their 16-source instantiations; SSSPY_ERR_UNSUPPORTED above 16).  n_basis K:
+ * the full-storage per-point kernels keep the bin's N spatial matrices and N basis rows in LDS and
+ * the spatial sums a row per frame of their 64-frame chunk, so every entry point returns
+ * SSSPY_ERR_UNSUPPORTED, before it touches anything, unless
+ *   N M^2 16 + N K 8 + 64 (2 M^2 + s) 8 <= 160 KB   (s = 16 above 8 sources at 2 and 3 channels, else 8)
+ * -- K <= 2424 at 8 sources and 2 channels, 1344 at 8 and 8, 608 at 16 and 8 (ssspy_gmnmf_route
+ * answers for a shape).  Above 48 KB the kernels' dynamic-LDS attribute is raised, at any source
+ * count.  n_channels M in [2, 8]: one lane per
  * (bin, frame) point or per spatial matrix; from 4 channels on the point lives in one packed
  * Hermitian matrix inverted in place (herm_packed.hpp) and the full-storage kernels only redo the
  * blocks whose points leave the fast route of to_psd (flags in the workspace).
@@ -879,12 +886,74 @@ enum {
 
 size_t ssspy_gmnmf_workspace_bytes(int B, int N, int M, int F, int T, int K);
 
+/* Which kernel forms the GaussMNMF entry points take for a shape (host only, launches nothing; ABI
+ * version 6): for tests and tools that must know which launcher branch a case exercises.  A
+ * projection of the launch plan the entry points obey (csrc/gmnmf_plan.hpp).  `partitioning`: the
+ * caller passes latent variables.  Returns 0, or -1 for arguments the entry points reject (the LDS
+ * bound above included, and n_basis > SSSPY_MAX_PARTITION_BASIS with partitioning: the LATENT step).
+ * plan (may be NULL): SSSPY_GMNMF_PLAN_INTS ints at the SSSPY_GMNMF_PLAN_* indices (a byte count that
+ * does not fit an int reads -1):
+ *   PACKED          4..8 channels: traces, loss, separate and the spatial sums run their packed *_p
+ *                   kernels first; the full-storage kernels redo the 128-frame blocks whose flag
+ *                   word was raised (separate: the points marked NaN in source 0).  0: 2 and 3
+ *                   channels, full-storage kernels alone
+ *   TRACE_SOURCES   sources k_gmnmf_traces_p is compiled for: 4 (N <= 4), 8, or 0 (not PACKED)
+ *   WIDE            9..16 sources: the GM_NWIDE forms (two groups of 8, lambda_n formed again)
+ *   SPATIAL_FORM    SSSPY_GMNMF_SPATIAL_LITERAL (2, 3 channels), _PACKED (4..6:
+ *                   k_gmnmf_spatial_update_p), _ROWS8 (7, 8: k_gmnmf_spatial_update_rows); the two
+ *                   packed forms leave flagged blocks of 64 matrices to the literal kernel
+ *   BASIS_FORM      k_gmnmf_basis: SSSPY_GMNMF_BASIS_REGISTERS (T <= 512: the bin's rows of A / Bt in
+ *                   registers), _LDS_TILE (T <= 4096), _MEMORY (above: the activation from memory)
+ *   BASIS_KC        basis indices it stages in LDS at a time, floor(4096 / T) (0: _MEMORY)
+ *   BASIS_BPW       bins per wave, 1..16 (a workgroup takes 4 BASIS_BPW bins)
+ *   ACT_CHUNKS, ACT_BINS_PER_CHUNK   bin chunks of the activation sums (slabs folded in chunk
+ *                   order) and ceil(F / chunks) bins of each; trailing chunks may hold fewer, or none
+ *   ACT_KSLABS      launches of 8 basis indices, ceil(K / 8)
+ *   BIN_LDS_BYTES   dynamic LDS of the full-storage traces / loss / separate kernels
+ *   LATENT_LDS_BYTES  of the latent update, N K 8 (0 without partitioning)
+ *   FLAGS_OFFSET    byte offset of the flag words in the workspace of ssspy_gmnmf_update
+ *   POINT_BLOCKS    flag words of the per-point kernels, ceil(T / 128) F B, [b][i][frame block]
+ *   MATRIX_BLOCKS   flag words of the spatial update (the same words), ceil(B N F / 64)
+ *   LOSS_FLAGS_OFFSET  byte offset of the POINT_BLOCKS flag words in the workspace of ssspy_gmnmf_loss */
+enum {
+  SSSPY_GMNMF_SPATIAL_LITERAL = 0,
+  SSSPY_GMNMF_SPATIAL_PACKED = 1,
+  SSSPY_GMNMF_SPATIAL_ROWS8 = 2,
+};
+enum {
+  SSSPY_GMNMF_BASIS_REGISTERS = 0,
+  SSSPY_GMNMF_BASIS_LDS_TILE = 1,
+  SSSPY_GMNMF_BASIS_MEMORY = 2,
+};
+enum {
+  SSSPY_GMNMF_PLAN_PACKED = 0,
+  SSSPY_GMNMF_PLAN_TRACE_SOURCES = 1,
+  SSSPY_GMNMF_PLAN_WIDE = 2,
+  SSSPY_GMNMF_PLAN_SPATIAL_FORM = 3,
+  SSSPY_GMNMF_PLAN_BASIS_FORM = 4,
+  SSSPY_GMNMF_PLAN_BASIS_KC = 5,
+  SSSPY_GMNMF_PLAN_BASIS_BPW = 6,
+  SSSPY_GMNMF_PLAN_ACT_CHUNKS = 7,
+  SSSPY_GMNMF_PLAN_ACT_BINS_PER_CHUNK = 8,
+  SSSPY_GMNMF_PLAN_ACT_KSLABS = 9,
+  SSSPY_GMNMF_PLAN_BIN_LDS_BYTES = 10,
+  SSSPY_GMNMF_PLAN_LATENT_LDS_BYTES = 11,
+  SSSPY_GMNMF_PLAN_FLAGS_OFFSET = 12,
+  SSSPY_GMNMF_PLAN_POINT_BLOCKS = 13,
+  SSSPY_GMNMF_PLAN_MATRIX_BLOCKS = 14,
+  SSSPY_GMNMF_PLAN_LOSS_FLAGS_OFFSET = 15,
+  SSSPY_GMNMF_PLAN_INTS = 16,
+};
+int ssspy_gmnmf_route(int B, int N, int M, int F, int T, int K, int partitioning, int *plan);
+
 /* The steps of update_once() selected by `steps`, in the reference's order: basis, activation,
  * spatial (H <- to_psd(P^-1 # H Q H), the matrix geometric mean of linalg/mean.py:6-83 type 2),
  * unit-trace normalisation of H with the scale moved into the basis, latent variables.
  * latent == NULL: basis (B,N,F,K), activation (B,N,K,T).  latent (B,N,K) given (partitioning):
  * basis (B,F,K) and activation (B,K,T) are shared, lambda_nij = sum_k z_nk t_ik v_kj, and the
- * normalisation leaves the basis alone.  ssspy_gmnmf_loss / _separate take the per-source pair
+ * normalisation leaves the basis alone (n_basis up to SSSPY_MAX_PARTITION_BASIS for the LATENT step:
+ * above, a call that selects it returns SSSPY_ERR_UNSUPPORTED before any step has run).
+ * ssspy_gmnmf_loss / _separate take the per-source pair
  * that ssspy_ilrma_partition_expand writes.
  * replaces: ssspy/bss/mnmf.py:806-834, :836-901, :903-968, :970-1016, :391-414, :1018-1073. */
 int ssspy_gmnmf_update(const void *X, double *basis, double *activation, double *latent,

@@ -29,13 +29,20 @@ MNMF_PLAN_FIELDS = ("fast", "ksmall", "basis_copy", "glds_cov", "glds_spatial", 
                     "tail_full", "tail_tail", "tail_split", "tail_groups", "htail_full", "htail_tail",
                     "htail_split", "htail_groups", "act_chunks", "ip1_records", "spatial_fold_in_norm",
                     "loss_slots", "logdet_slots")
+# SSSPY_GMNMF_PLAN_*: the names of the plan ints of ssspy_gmnmf_route; SSSPY_GMNMF_SPATIAL_* / _BASIS_*
+GMNMF_PLAN_FIELDS = ("packed", "trace_sources", "wide", "spatial_form", "basis_form", "basis_kc",
+                     "basis_bpw", "act_chunks", "act_bins_per_chunk", "act_kslabs", "bin_lds_bytes",
+                     "latent_lds_bytes", "flags_offset", "point_blocks", "matrix_blocks",
+                     "loss_flags_offset")
+GMNMF_SPATIAL_LITERAL, GMNMF_SPATIAL_PACKED, GMNMF_SPATIAL_ROWS8 = range(3)
+GMNMF_BASIS_REGISTERS, GMNMF_BASIS_LDS_TILE, GMNMF_BASIS_MEMORY = range(3)
 MAX_PAIRS = 32
 # SSSPY_MAX_SOURCES (per-N kernels: IPA, both MNMF classes, the Hermitian operators; GaussMNMF's
 # channels and the ILRMA partition entry points stop there), SSSPY_RT_MAX_SOURCES (run-time-N kernels:
 # the shared operators, ILRMA, AuxIVA, FastGaussMNMF's channels and sources, GaussMNMF's sources),
 # SSSPY_MAX_BASIS
 MAX_SOURCES, RT_MAX_SOURCES, MAX_BASIS = 8, 16, 65536
-ABI_VERSION = 5  # SSSPY_ABI_VERSION of the include/ssspy_amd.h these prototypes mirror
+ABI_VERSION = 6  # SSSPY_ABI_VERSION of the include/ssspy_amd.h these prototypes mirror
 
 _p, _i, _d, _z = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_size_t
 _q = ctypes.c_longlong
@@ -131,6 +138,7 @@ PROTOTYPES = {
     "ssspy_cacgmm_fold_loss": (_i, [_p, _p, _q, _i, _p]),
     "ssspy_cacgmm_separate": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "ssspy_gmnmf_workspace_bytes": (_z, [_i, _i, _i, _i, _i, _i]),
+    "ssspy_gmnmf_route": (_i, [_i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]),
     "ssspy_gmnmf_update": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _d, _p, _z, _p]),
     "ssspy_gmnmf_loss_workspace_bytes": (_z, [_i, _i, _i]),
     "ssspy_gmnmf_loss": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _p, _z, _p]),

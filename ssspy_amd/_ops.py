@@ -935,6 +935,18 @@ def gmnmf_workspace(B, N, M, F, T, K, dev):
     return _workspace(_L().ssspy_gmnmf_workspace_bytes(B, N, M, F, T, K), dev)
 
 
+def gmnmf_route(B, N, M, F, T, K, partitioning=False):
+    """What the launchers of the GaussMNMF entry points decide for this shape, as a dict over
+    _lib.GMNMF_PLAN_FIELDS (see ssspy_gmnmf_route in the header).  Host only; ValueError for a shape
+    the entry points reject."""
+    import ctypes
+
+    plan = (ctypes.c_int * len(_lib.GMNMF_PLAN_FIELDS))()
+    if int(_L().ssspy_gmnmf_route(B, N, M, F, T, K, 1 if partitioning else 0, plan)) < 0:
+        raise ValueError("gmnmf_route: shape rejected")
+    return dict(zip(_lib.GMNMF_PLAN_FIELDS, (int(v) for v in plan)))
+
+
 def gmnmf_update(X, basis, activation, spatial, steps, flooring, ws, ws_bytes, latent=None):
     B, M, F, T = X.shape
     N, K = spatial.shape[1], basis.shape[-1]

@@ -14,6 +14,7 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "gmnmf_plan.hpp"
 #include "hermitian.hpp"
 #include "herm_packed.hpp"
 #include "ssspy_amd.h"
@@ -21,15 +22,11 @@
 namespace ssspy {
 
 // gmnmf_rows.hip
-bool gmnmf_spatial_update_rows_wanted(int M);
 int gmnmf_spatial_update_rows(void *H, const double *PQ, long long count, int M, int floor_kind,
                               double eps, int *flags, hipStream_t st);
 
-constexpr int GM_NMAX = SSSPY_MAX_SOURCES;
-// 9..16 sources: the per-point kernels below take the source bound NX as a template parameter, GM_NMAX
-// (every shape up to 8 sources, unchanged) or GM_NWIDE (only when N > 8)
-constexpr int GM_NWIDE = SSSPY_RT_MAX_SOURCES;
-static_assert(GM_NWIDE == 2 * GM_NMAX, "the wide forms walk the sources in two groups of GM_NMAX");
+// (GM_NMAX, GM_NWIDE -- the source bound NX of the per-point kernels below -- and the other launch
+// constants are in gmnmf_plan.hpp, with every decision the launchers take)
 
 // coefficients of XX = c1 x x^H + c0 I after the eigenvalue floor
 __device__ __forceinline__ void xx_floor_coeffs(double s, int floor_kind, double eps, double &c1,
@@ -295,16 +292,7 @@ __device__ __forceinline__ double wave_sum_dpp(double v) {
   return __hiloint2double(hi, lo);
 }
 
-constexpr int GMB_LDS = 4096;     // staged activation values (32 KB)
-// bins per wave: up to 16, fewer while that leaves the launch under ~2048 workgroups
-static inline int gmb_bins_per_wave(int B, int N, int F) {
-  const long long rows = (long long)B * N * F;
-  long long bpw = rows / (4 * 2048);
-  if (bpw < 1) bpw = 1;
-  if (bpw > 16) bpw = 16;
-  return (int)bpw;
-}
-
+// (GMB_LDS staged activation values, bpw bins per wave: gmnmf_plan.hpp)
 __global__ __launch_bounds__(256) void k_gmnmf_basis(double *basis, const double *__restrict__ act,
                                                      const double *__restrict__ A,
                                                      const double *__restrict__ Bt, int N, int F,
@@ -329,6 +317,7 @@ __global__ __launch_bounds__(256) void k_gmnmf_basis(double *basis, const double
         const long long row = (((long long)b * N + n) * F + i) * T;
         // the row's traces stay in registers over the basis walk while they fit (T <= 512)
         constexpr int MT = 8;
+        static_assert(64 * MT == GMB_REG_FRAMES, "the plan names the register form by this bound");
         double ar[MT], br[MT];
         const bool in_regs = T <= 64 * MT;
         if (in_regs) {
@@ -556,8 +545,7 @@ __global__ __launch_bounds__(256) void k_gmnmf_activation_apply(double *act,
 // stored packed as M*M doubles (diagonal, then re/im of the upper triangle).  grid: (F, B), one
 // wave: lanes take frames, the per-chunk matrices go through LDS and thread (n, entry) folds the
 // chunk with the N weights.
-constexpr int GM_PB = 64;  // points per chunk (= block size of k_gmnmf_spatial_acc)
-
+// GM_PB points per chunk (= block size of k_gmnmf_spatial_acc)
 template <int M>
 __device__ __forceinline__ void pack_hermitian(const c128 (&A)[M][M], double *dst) {
   int e = 0;
@@ -1188,7 +1176,7 @@ __global__ __launch_bounds__(128) void k_gmnmf_separate_p(const c128 *__restrict
 // kernel reads two values per FMA, and its 70 KB of LDS at 8 channels leave half the SIMDs idle).
 // From GM_SPLIT_FROM channels on the two matrices of a point (R^-1, then R^-1 XX R^-1) take turns in
 // the rows: 37 KB per workgroup at 8 channels (one workgroup per SIMD), 13 KB at 4.
-constexpr int GM_SPLIT_FROM = 4;  // channels from which the two matrices take turns in the rows
+// (GM_SPLIT_FROM: gmnmf_plan.hpp)
 constexpr int gm_pow2_floor(int v) { return v >= 8 ? 8 : (v >= 4 ? 4 : (v >= 2 ? 2 : 1)); }
 
 // NX = GM_NWIDE: 16 weights per row, so NPT doubles: 2 at 4 channels, 4 at 5, 8 at 6-8 (32
@@ -1336,7 +1324,7 @@ __global__ __launch_bounds__(GM_PB) void k_gmnmf_spatial_acc_p(const c128 *__res
 // ||U^-1||_F^2 < 1 / eps); a block of 64 matrices with any failure stores nothing, raises its flag
 // and is redone by the literal kernel.  One lane per (b, n, i); the block's H matrices are staged
 // in LDS ([entry][lane], coalesced both ways) and the region then parks U^-1 during the sweeps.
-constexpr int GSU_LD = 65;  // lanes per staged entry + 1: the transposing copies hit distinct banks
+// (GSU_LD lanes per staged entry: gmnmf_plan.hpp)
 // c128 entries of the region per lane: the M x M matrix, or (two turns) the rows of the first turn
 // followed by the parked S0 (M^2 doubles)
 template <int M>
@@ -1588,59 +1576,6 @@ __global__ __launch_bounds__(64) void k_gmnmf_spatial_update_p(c128 *H,
   }
 }
 
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct GmnmfWs {
-  size_t a, bt, pq, vacc, teff, vrep, raw, vslabs, flags, hq, total;
-};
-// bin chunks of the activation sums: enough blocks for the chip at small batches, at most 16
-static inline int gm_act_chunks(int B, int N, int F, int T) {
-  const long long blocks0 = (long long)((T + 63) / 64) * N * B;
-  long long want = (1024 + blocks0 - 1) / blocks0;
-  if (want > 16) want = 16;
-  if (want > (F + 7) / 8) want = (F + 7) / 8;  // at least 8 bins per chunk
-  return want < 1 ? 1 : (int)want;
-}
-// source slots per bin of the packed spatial parts Hq (and the NX of the per-point kernels)
-static inline int gm_nx(int N) { return N > GM_NMAX ? GM_NWIDE : GM_NMAX; }
-
-static inline GmnmfWs gmnmf_ws(int B, int N, int M, int F, int T, int K) {
-  GmnmfWs w;
-  size_t off = 0;
-  w.a = off;
-  off += align256((size_t)B * N * F * T * sizeof(double));
-  w.bt = off;
-  off += align256((size_t)B * N * F * T * sizeof(double));
-  w.pq = off;  // packed Hermitian sums of the spatial update
-  off += align256((size_t)B * N * F * M * M * 2 * sizeof(double));
-  w.vacc = off;  // activation sums (num, den)
-  off += align256((size_t)B * N * 2 * K * T * sizeof(double));
-  w.teff = off;  // partitioning: expanded pair and the (num, den) basis sums
-  off += align256((size_t)B * N * F * K * sizeof(double));
-  w.vrep = off;
-  off += align256((size_t)B * N * K * T * sizeof(double));
-  w.raw = off;
-  off += align256((size_t)B * N * F * K * 2 * sizeof(double));
-  w.vslabs = off;  // per-chunk slabs of the activation sums + the scratch of their fold
-  {
-    const int chunks = gm_act_chunks(B, N, F, T);
-    const long long vtotal = 2ll * B * N * K * T;
-    off += chunks > 1 ? align256((size_t)chunks * vtotal * sizeof(double) +
-                                 fold_scratch_bytes(vtotal, chunks))
-                      : 0;
-  }
-  w.flags = off;  // one int per block of the per-point kernels: left the fast route (packed path)
-  off += align256((size_t)((T + 127) / 128) * F * B * sizeof(int));
-  w.hq = off;  // packed symmetric parts of the spatial matrices, [b][i][gm_nx(N)][M M] (packed path)
-  off += align256((size_t)B * F * gm_nx(N) * M * M * sizeof(double));
-  w.total = off;
-  return w;
-}
-
-static inline size_t bin_smem(int N, int M, int K) {
-  return (size_t)N * M * M * sizeof(c128) + (size_t)((N * K + 1) & ~1) * sizeof(double);
-}
-
 // (variadic: GM_DISPATCH_MN hands it a call already expanded, commas and all)
 #define GM_DISPATCH_M(M_, ...)                                                               \
   switch (M_) {                                                                              \
@@ -1664,49 +1599,30 @@ static inline size_t bin_smem(int N, int M, int K) {
     GM_DISPATCH_M(M_, __VA_ARGS__);    \
   }
 
-constexpr size_t GM_LDS_MAX = 160 * 1024;  // LDS a workgroup may take on gfx950
-
 static int lds_attribute(const void *fn, size_t bytes) {
-  if (bytes <= 48 * 1024) return SSSPY_OK;
+  if (bytes <= GM_LDS_DEFAULT) return SSSPY_OK;
   hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   return e == hipSuccess ? SSSPY_OK : fail(SSSPY_ERR_HIP, hipGetErrorString(e));
 }
 
-static int check_dims(int B, int N, int M, int F, int T, int K) {
-  SSSPY_REQUIRE(B > 0 && F > 0 && T > 0, "GaussMNMF: bad shape");
-  SSSPY_REQUIRE(N >= 1, "GaussMNMF: n_sources must be in [1, 16]");
-  if (N > GM_NWIDE) return fail(SSSPY_ERR_UNSUPPORTED, "GaussMNMF: n_sources must be in [1, 16]");
-  SSSPY_REQUIRE(K >= 1 && K <= SSSPY_MAX_BASIS, "GaussMNMF: n_basis must be in [1, 65536]");
-  if (M < 2 || M > 8) return fail(SSSPY_ERR_UNSUPPORTED, "GaussMNMF: n_channels must be in [2, 8]");
-  if (N > GM_NMAX) {
-    // the full-storage kernels stage the bin's N spatial matrices and N basis rows in LDS; the
-    // spatial sums add a row per frame of the chunk (k_gmnmf_spatial_acc)
-    const int ns = M >= 4 ? GM_NMAX : GM_NWIDE;
-    const size_t acc = bin_smem(N, M, K) + (size_t)GM_PB * (2 * M * M + ns) * sizeof(double);
-    if (acc > GM_LDS_MAX)
-      return fail(SSSPY_ERR_UNSUPPORTED,
-                  "GaussMNMF: above 8 sources n_basis is bounded by the 160 KB of LDS of a "
-                  "workgroup (the bin's spatial matrices and basis rows)");
-    int rc = SSSPY_OK;
-    const size_t bin = bin_smem(N, M, K);
-    GM_DISPATCH_M(M, {
-      rc = lds_attribute((const void *)k_gmnmf_traces<MM, GM_NWIDE>, bin);
-      if (!rc) rc = lds_attribute((const void *)k_gmnmf_loss<MM, GM_NWIDE>, bin);
-      if (!rc) rc = lds_attribute((const void *)k_gmnmf_separate<MM, GM_NWIDE>, bin);
-    });
-    if (rc) return rc;
-  }
-  return SSSPY_OK;
+// The plan's verdict on the shape, then -- at any source count -- the dynamic-LDS attribute of the
+// full-storage per-point kernels where the bin's spatial matrices and basis rows take more than the
+// 48 KB a kernel gets without it (the plan has bounded them by the 160 KB of a workgroup).
+static int check_plan(const GmnmfPlan &p, int N, int M) {
+  if (p.status != SSSPY_OK) return fail(p.status, p.why);
+  if (p.bin_lds <= GM_LDS_DEFAULT) return SSSPY_OK;
+  int rc = SSSPY_OK;
+  GM_DISPATCH_MN(M, N, {
+    rc = lds_attribute((const void *)k_gmnmf_traces<MM, NX>, p.bin_lds);
+    if (!rc) rc = lds_attribute((const void *)k_gmnmf_loss<MM, NX>, p.bin_lds);
+    if (!rc) rc = lds_attribute((const void *)k_gmnmf_separate<MM, NX>, p.bin_lds);
+  });
+  return rc;
 }
 
-// SSSPY_AMD_GMNMF_FULL=1: the full-storage kernels only (A / B, debugging)
-// (2 and 3 channels keep the full-storage kernels: nothing spills there and the packed route's
-// extra launches -- packing, the flag-gated repair kernels -- cost 10 % of a 0.15-0.25 ms iteration)
-static bool packed_points(int M) { return M >= 4; }
-
-static int launch_pack_spatial(const void *H, double *Hq, int B, int N, int M, int F,
-                               hipStream_t st) {
-  const long long count = (long long)B * F * gm_nx(N) * M * M;
+static int launch_pack_spatial(const GmnmfPlan &p, const void *H, double *Hq, int B, int N, int M,
+                               int F, hipStream_t st) {
+  const long long count = (long long)B * F * p.nx * M * M;
   GM_DISPATCH_MN(M, N, hipLaunchKernelGGL((k_gm_pack_spatial<MM, NX>),
                                           dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st,
                                           (const c128 *)H, Hq, N, F, count));
@@ -1714,22 +1630,22 @@ static int launch_pack_spatial(const void *H, double *Hq, int B, int N, int M, i
 }
 
 // flags, Hq: workspace of the packed path (both or neither)
-static int launch_traces(const void *X, const double *basis, const double *act, const void *H,
-                         double *A, double *Bt, int B, int N, int M, int F, int T, int K,
-                         int floor_kind, double eps, int *flags, double *Hq, bool *hq_valid,
+static int launch_traces(const GmnmfPlan &p, const void *X, const double *basis, const double *act,
+                         const void *H, double *A, double *Bt, int B, int N, int M, int F, int T,
+                         int K, int floor_kind, double eps, int *flags, double *Hq, bool *hq_valid,
                          hipStream_t st) {
-  dim3 grid((T + 127) / 128, F, B), block(128);
-  const bool packed = packed_points(M) && flags != nullptr && Hq != nullptr;
+  dim3 grid((T + GM_POINT_BLOCK - 1) / GM_POINT_BLOCK, F, B), block(GM_POINT_BLOCK);
+  const bool packed = p.packed;
   if (packed) {
     int rc = SSSPY_OK;
-    if (!*hq_valid) rc = launch_pack_spatial(H, Hq, B, N, M, F, st);
+    if (!*hq_valid) rc = launch_pack_spatial(p, H, Hq, B, N, M, F, st);
     if (rc) return rc;
     *hq_valid = true;
-    if (N <= 4) {
+    if (p.trace_sources == 4) {
       GM_DISPATCH_M(M, hipLaunchKernelGGL((k_gmnmf_traces_p<MM, 4>), grid, block, 0, st,
                                           (const c128 *)X, basis, act, (const double *)Hq, A, Bt,
                                           N, F, T, K, floor_kind, eps, flags));
-    } else if (N <= GM_NMAX) {
+    } else if (!p.wide) {
       GM_DISPATCH_M(M, hipLaunchKernelGGL((k_gmnmf_traces_p<MM, 8>), grid, block, 0, st,
                                           (const c128 *)X, basis, act, (const double *)Hq, A, Bt,
                                           N, F, T, K, floor_kind, eps, flags));
@@ -1742,7 +1658,7 @@ static int launch_traces(const void *X, const double *basis, const double *act, 
     if (rc) return rc;
   }
   GM_DISPATCH_MN(M, N, hipLaunchKernelGGL((k_gmnmf_traces<MM, NX>), grid, block,
-                                          bin_smem(N, M, K), st, (const c128 *)X, basis, act,
+                                          p.bin_lds, st, (const c128 *)X, basis, act,
                                           (const c128 *)H, A, Bt, N, F, T, K, floor_kind, eps,
                                           packed ? (const int *)flags : nullptr));
   return check_launch("k_gmnmf_traces");
@@ -1756,7 +1672,8 @@ extern "C" {
 
 size_t ssspy_gmnmf_workspace_bytes(int B, int N, int M, int F, int T, int K) {
   if (B <= 0 || N <= 0 || M <= 0 || F <= 0 || T <= 0 || K <= 0) return 0;
-  return gmnmf_ws(B, N, M, F, T, K).total;
+  // (sized for any positive shape, as before the plan: the entry points judge the shape)
+  return gmnmf_ws(B, N, M, F, T, K, gm_source_slots(N), gm_act_chunks(B, N, F, T)).total;
 }
 
 int ssspy_gmnmf_update(const void *X, double *basis, double *activation, double *latent,
@@ -1765,9 +1682,12 @@ int ssspy_gmnmf_update(const void *X, double *basis, double *activation, double 
                        void *stream) {
   SSSPY_REQUIRE(X && basis && activation && spatial, "gmnmf_update: null argument");
   SSSPY_REQUIRE(latent || !(steps & SSSPY_GMNMF_LATENT), "gmnmf_update: latent step without latent");
-  int rc = check_dims(B, N, M, F, T, K);
+  const GmnmfPlan plan = make_gmnmf_plan(B, N, M, F, T, K, latent != nullptr);
+  int rc = check_plan(plan, N, M);
   if (rc) return rc;
-  const GmnmfWs w = gmnmf_ws(B, N, M, F, T, K);
+  if ((steps & SSSPY_GMNMF_LATENT) && !plan.latent_ok)  // (refused before any step has run)
+    return fail(SSSPY_ERR_UNSUPPORTED, "GaussMNMF: partitioning takes n_basis up to 1024");
+  const GmnmfWs &w = plan.ws;
   SSSPY_REQUIRE(workspace && workspace_bytes >= w.total, "gmnmf_update: workspace too small");
   char *ws = (char *)workspace;
   double *A = (double *)(ws + w.a), *Bt = (double *)(ws + w.bt);
@@ -1794,10 +1714,10 @@ int ssspy_gmnmf_update(const void *X, double *basis, double *activation, double 
   auto basis_sums = [&](double *raw_out) -> int {
     int r = refresh();
     if (r) return r;
-    r = launch_traces(X, Tn, Vn, spatial, A, Bt, B, N, M, F, T, K, floor_kind, floor_eps, flags, Hq, &hq_valid, st);
+    r = launch_traces(plan, X, Tn, Vn, spatial, A, Bt, B, N, M, F, T, K, floor_kind, floor_eps, flags, Hq, &hq_valid, st);
     if (r) return r;
     {
-      const int bpw = gmb_bins_per_wave(B, N, F);
+      const int bpw = plan.basis_bpw;
       hipLaunchKernelGGL(k_gmnmf_basis, dim3((F + 4 * bpw - 1) / (4 * bpw), N, B), dim3(256), 0, st,
                        basis, Vn,
                        (const double *)A, (const double *)Bt, N, F, T, K, floor_kind, floor_eps,
@@ -1819,14 +1739,14 @@ int ssspy_gmnmf_update(const void *X, double *basis, double *activation, double 
   if (steps & SSSPY_GMNMF_ACTIVATION) {
     rc = refresh();
     if (rc) return rc;
-    rc = launch_traces(X, Tn, Vn, spatial, A, Bt, B, N, M, F, T, K, floor_kind, floor_eps, flags, Hq, &hq_valid, st);
+    rc = launch_traces(plan, X, Tn, Vn, spatial, A, Bt, B, N, M, F, T, K, floor_kind, floor_eps, flags, Hq, &hq_valid, st);
     if (rc) return rc;
     const long long count = (long long)B * N * K * T;
-    const int chunks = gm_act_chunks(B, N, F, T);
-    const int bpc = (F + chunks - 1) / chunks;
+    const int chunks = plan.act_chunks;
+    const int bpc = plan.act_bins_per_chunk;
     const long long vtotal = 2 * count;  // (num, den) sums
     double *slabs = chunks > 1 ? (double *)(ws + w.vslabs) : vacc;
-    for (int k0 = 0; k0 < K; k0 += 8) {
+    for (int k0 = 0; k0 < K; k0 += GM_ACT_KSLAB) {
       hipLaunchKernelGGL(k_gmnmf_activation_sums, dim3((T + 63) / 64, chunks, N * B), dim3(256), 0,
                          st, Tn, (const double *)A, (const double *)Bt, slabs, N, F, T, K, k0, bpc,
                          vtotal);
@@ -1855,24 +1775,26 @@ int ssspy_gmnmf_update(const void *X, double *basis, double *activation, double 
     rc = refresh();
     if (rc) return rc;
     GM_DISPATCH_MN(M, N, {
-      const size_t smem = bin_smem(N, M, K) +
-                          (size_t)GM_PB * (2 * MM * MM + gm_acc_sources<MM, NX>()) * sizeof(double);
-      if (smem > 48 * 1024) {  // 8 channels: 64 points x 136 doubles; gfx950 has 160 KB per CU
+      static_assert(gm_acc_sources<MM, NX>() == ((MM >= 4 && NX > GM_NMAX) ? GM_NMAX : NX),
+                    "the plan's acc_sources restates gm_acc_sources");
+      const size_t smem = plan.acc_lds;
+      if (smem > GM_LDS_DEFAULT) {  // 8 channels: 64 points x 136 doubles; gfx950 has 160 KB per CU
         hipError_t e = hipFuncSetAttribute((const void *)k_gmnmf_spatial_acc<MM, NX>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e != hipSuccess) return fail(SSSPY_ERR_HIP, hipGetErrorString(e));
       }
-      const bool packed = packed_points(M);
+      const bool packed = plan.packed;
       if (packed) {
-        const int ew_p = MM >= GM_SPLIT_FROM ? ((MM * MM + 1) & ~1) : 2 * MM * MM;
-        const size_t smem_p = (size_t)GM_PB * (ew_p + NX + 1) * sizeof(double);
-        if (smem_p > 48 * 1024) {
+        static_assert(gm_acc_p_row(MM, NX) == GmFold<gm_acc_p_values(MM), NX>::ROW,
+                      "the plan's acc_p_lds restates the rows of k_gmnmf_spatial_acc_p");
+        const size_t smem_p = plan.acc_p_lds;
+        if (smem_p > GM_LDS_DEFAULT) {
           hipError_t e = hipFuncSetAttribute((const void *)k_gmnmf_spatial_acc_p<MM, NX>,
                                              hipFuncAttributeMaxDynamicSharedMemorySize,
                                              (int)smem_p);
           if (e != hipSuccess) return fail(SSSPY_ERR_HIP, hipGetErrorString(e));
         }
-        if (!hq_valid) rc = launch_pack_spatial(spatial, Hq, B, N, M, F, st);
+        if (!hq_valid) rc = launch_pack_spatial(plan, spatial, Hq, B, N, M, F, st);
         if (rc) return rc;
         hq_valid = true;
         hipLaunchKernelGGL((k_gmnmf_spatial_acc_p<MM, NX>), dim3(F, B), dim3(GM_PB), smem_p, st,
@@ -1886,8 +1808,8 @@ int ssspy_gmnmf_update(const void *X, double *basis, double *activation, double 
     rc = check_launch("k_gmnmf_spatial_acc");
     if (rc) return rc;
     const long long count = (long long)B * N * F;
-    const bool packed_su = packed_points(M);
-    if (packed_su && gmnmf_spatial_update_rows_wanted(M)) {
+    const bool packed_su = plan.spatial_form != GmSpatialForm::Literal;
+    if (plan.spatial_form == GmSpatialForm::Rows8) {
       // 7 / 8 channels: a matrix on 8 lanes (gmnmf_rows.hip); same flags, same repair kernel below
       rc = gmnmf_spatial_update_rows(spatial, (const double *)PQ, count, M, floor_kind, floor_eps,
                                      flags, st);
@@ -1898,8 +1820,9 @@ int ssspy_gmnmf_update(const void *X, double *basis, double *activation, double 
       switch (M) {
 #define SSSPY_GSU_P(MM_)                                                                         \
   case MM_: {                                                                                    \
-    const size_t smem_su = (size_t)gsu_entries<MM_>() * GSU_LD * sizeof(c128);                   \
-    if (smem_su > 48 * 1024) {                                                                   \
+    static_assert(gsu_entries<MM_>() == MM_ * MM_, "the plan's update_p_lds restates this");     \
+    const size_t smem_su = plan.update_p_lds;                                                    \
+    if (smem_su > GM_LDS_DEFAULT) {                                                              \
       hipError_t e = hipFuncSetAttribute((const void *)k_gmnmf_spatial_update_p<MM_>,            \
                                          hipFuncAttributeMaxDynamicSharedMemorySize,             \
                                          (int)smem_su);                                          \
@@ -1935,12 +1858,9 @@ int ssspy_gmnmf_update(const void *X, double *basis, double *activation, double 
     hq_valid = false;
   }
   if (steps & SSSPY_GMNMF_LATENT) {
-    // (the latent variables of all sources sit in the LDS of one workgroup)
-    if (K > SSSPY_MAX_PARTITION_BASIS)
-      return fail(SSSPY_ERR_UNSUPPORTED, "GaussMNMF: partitioning takes n_basis up to 1024");
     rc = basis_sums(raw);
     if (rc) return rc;
-    const size_t smem_z = (size_t)N * K * sizeof(double);  // up to 128 KB at 16 sources
+    const size_t smem_z = plan.latent_lds;  // up to 128 KB at 16 sources
     rc = lds_attribute((const void *)k_gm_part_latent, smem_z);
     if (rc) return rc;
     hipLaunchKernelGGL(k_gm_part_latent, dim3(B), dim3(256), smem_z, st,
@@ -1954,9 +1874,7 @@ int ssspy_gmnmf_update(const void *X, double *basis, double *activation, double 
 
 size_t ssspy_gmnmf_loss_workspace_bytes(int B, int F, int T) {
   if (B <= 0 || F <= 0 || T <= 0) return 0;
-  // the loss slots, then one flag per block (packed path)
-  return align256(scalar_slots_bytes(B, ((T + 127) / 128) * F)) +
-         align256((size_t)((T + 127) / 128) * F * B * sizeof(int));
+  return gmnmf_loss_ws(B, F, T).total;
 }
 
 int ssspy_gmnmf_loss(const void *X, const double *basis, const double *activation,
@@ -1964,15 +1882,16 @@ int ssspy_gmnmf_loss(const void *X, const double *basis, const double *activatio
                      int floor_kind, double floor_eps, void *workspace, size_t workspace_bytes,
                      void *stream) {
   SSSPY_REQUIRE(X && basis && activation && spatial && out, "gmnmf_loss: null argument");
-  int rc = check_dims(B, N, M, F, T, K);
+  const GmnmfPlan plan = make_gmnmf_plan(B, N, M, F, T, K, false);
+  int rc = check_plan(plan, N, M);
   if (rc) return rc;
-  SSSPY_REQUIRE(workspace && workspace_bytes >= ssspy_gmnmf_loss_workspace_bytes(B, F, T),
+  SSSPY_REQUIRE(workspace && workspace_bytes >= plan.loss_ws_total,
                 "gmnmf_loss: workspace too small (ssspy_gmnmf_loss_workspace_bytes)");
   hipStream_t st = as_stream(stream);
-  dim3 grid((T + 127) / 128, F, B), block(128);
+  dim3 grid((T + GM_POINT_BLOCK - 1) / GM_POINT_BLOCK, F, B), block(GM_POINT_BLOCK);
   // (every block writes its slot; the fold stores out[b])
-  int *flags = (int *)((char *)workspace + align256(scalar_slots_bytes(B, (int)grid.x * F)));
-  const bool packed = packed_points(M);
+  int *flags = (int *)((char *)workspace + plan.loss_flags_offset);
+  const bool packed = plan.packed;
   if (packed) {
     GM_DISPATCH_MN(M, N, hipLaunchKernelGGL((k_gmnmf_loss_p<MM, NX>), grid, block, 0, st,
                                             (const c128 *)X, basis, activation,
@@ -1982,7 +1901,7 @@ int ssspy_gmnmf_loss(const void *X, const double *basis, const double *activatio
     if (rc) return rc;
   }
   GM_DISPATCH_MN(M, N, hipLaunchKernelGGL((k_gmnmf_loss<MM, NX>), grid, block,
-                                          bin_smem(N, M, K), st, (const c128 *)X, basis,
+                                          plan.bin_lds, st, (const c128 *)X, basis,
                                           activation, (const c128 *)spatial, (double *)workspace,
                                           N, F, T, K, floor_kind, floor_eps,
                                           packed ? (const int *)flags : nullptr));
@@ -1994,11 +1913,12 @@ int ssspy_gmnmf_separate(const void *X, const double *basis, const double *activ
                          const void *spatial, void *Y, int B, int N, int M, int F, int T, int K,
                          int reference_id, int floor_kind, double floor_eps, void *stream) {
   SSSPY_REQUIRE(X && basis && activation && spatial && Y, "gmnmf_separate: null argument");
-  int rc = check_dims(B, N, M, F, T, K);
+  const GmnmfPlan plan = make_gmnmf_plan(B, N, M, F, T, K, false);
+  int rc = check_plan(plan, N, M);
   if (rc) return rc;
   SSSPY_REQUIRE(reference_id >= 0 && reference_id < M, "gmnmf_separate: bad reference_id");
-  dim3 grid((T + 127) / 128, F, B), block(128);
-  const bool packed = packed_points(M);
+  dim3 grid((T + GM_POINT_BLOCK - 1) / GM_POINT_BLOCK, F, B), block(GM_POINT_BLOCK);
+  const bool packed = plan.packed;
   if (packed) {
     GM_DISPATCH_MN(M, N, hipLaunchKernelGGL((k_gmnmf_separate_p<MM, NX>), grid, block, 0,
                                             as_stream(stream), (const c128 *)X, basis, activation,
@@ -2008,11 +1928,37 @@ int ssspy_gmnmf_separate(const void *X, const double *basis, const double *activ
     if (rc) return rc;
   }
   GM_DISPATCH_MN(M, N, hipLaunchKernelGGL((k_gmnmf_separate<MM, NX>), grid, block,
-                                          bin_smem(N, M, K), as_stream(stream), (const c128 *)X,
+                                          plan.bin_lds, as_stream(stream), (const c128 *)X,
                                           basis, activation, (const c128 *)spatial, (c128 *)Y, N,
                                           F, T, K, reference_id, floor_kind, floor_eps,
                                           packed ? 1 : 0));
   return check_launch("k_gmnmf_separate");
+}
+
+int ssspy_gmnmf_route(int B, int N, int M, int F, int T, int K, int partitioning, int *plan) {
+  const GmnmfPlan p = make_gmnmf_plan(B, N, M, F, T, K, partitioning != 0);
+  if (p.status != SSSPY_OK || (partitioning && !p.latent_ok)) return -1;
+  if (plan) {
+    int v[SSSPY_GMNMF_PLAN_INTS];
+    v[SSSPY_GMNMF_PLAN_PACKED] = p.packed ? 1 : 0;
+    v[SSSPY_GMNMF_PLAN_TRACE_SOURCES] = p.trace_sources;
+    v[SSSPY_GMNMF_PLAN_WIDE] = p.wide ? 1 : 0;
+    v[SSSPY_GMNMF_PLAN_SPATIAL_FORM] = (int)p.spatial_form;
+    v[SSSPY_GMNMF_PLAN_BASIS_FORM] = (int)p.basis_form;
+    v[SSSPY_GMNMF_PLAN_BASIS_KC] = p.basis_kc;
+    v[SSSPY_GMNMF_PLAN_BASIS_BPW] = p.basis_bpw;
+    v[SSSPY_GMNMF_PLAN_ACT_CHUNKS] = p.act_chunks;
+    v[SSSPY_GMNMF_PLAN_ACT_BINS_PER_CHUNK] = p.act_bins_per_chunk;
+    v[SSSPY_GMNMF_PLAN_ACT_KSLABS] = p.act_kslabs;
+    v[SSSPY_GMNMF_PLAN_BIN_LDS_BYTES] = gm_plan_int(p.bin_lds);
+    v[SSSPY_GMNMF_PLAN_LATENT_LDS_BYTES] = gm_plan_int(p.latent_lds);
+    v[SSSPY_GMNMF_PLAN_FLAGS_OFFSET] = gm_plan_int(p.ws.flags);
+    v[SSSPY_GMNMF_PLAN_POINT_BLOCKS] = gm_plan_int((unsigned long long)p.point_blocks);
+    v[SSSPY_GMNMF_PLAN_MATRIX_BLOCKS] = gm_plan_int((unsigned long long)p.matrix_blocks);
+    v[SSSPY_GMNMF_PLAN_LOSS_FLAGS_OFFSET] = gm_plan_int(p.loss_flags_offset);
+    for (int e = 0; e < SSSPY_GMNMF_PLAN_INTS; ++e) plan[e] = v[e];
+  }
+  return 0;
 }
 
 }  // extern "C"
