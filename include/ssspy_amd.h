@@ -95,8 +95,9 @@ const char *ssspy_amd_version(void);
  *    ssspy_ilrma_deferred_logdet_slots added).
  * 4: the ssspy_cacgmm_* entry points added.
  * 5: ssspy_fastmnmf_route added (additive: no existing argument list changed).
- * 6: ssspy_gmnmf_route added (additive). */
-#define SSSPY_ABI_VERSION 6
+ * 6: ssspy_gmnmf_route added (additive).
+ * 7: the FastIVA / FasterIVA entry points and ssspy_whitening_filter added (additive). */
+#define SSSPY_ABI_VERSION 7
 int ssspy_abi_version(void);
 const char *ssspy_last_error(void);
 
@@ -620,6 +621,57 @@ int ssspy_iva_grad_step_logdet_slots(int B, int F, int N);
 int ssspy_iva_grad_step(void *W, const void *stats, int stats_ready, int B, int F, int N,
                         int natural, int holonomic, double step_size, int *info, double *logdet,
                         long long logdet_stride, void *stream);
+
+/* ------------------------------------------------- FastIVA / FasterIVA, whitening, PCA */
+
+/* The fixed-point IVA classes work on the whitened mixture Z (B,N,F,T) with unitary filters W
+ * (B,F,N,N); 2..16 sources (2..8 compiled per count, 9..16 with the count at run time; correct, not
+ * tuned), SSSPY_ERR_UNSUPPORTED outside.  fp64 / complex128, no atomics on doubles, every sum in a
+ * fixed order.  info (device int, may be NULL) is bumped once per bin a step cannot finish. */
+
+/* phi[b,n,j] = d_contrast / floor(2 r), psi[b,n,j] = (2 phi - dd_contrast) / floor(2 r) with
+ * r = sqrt(r2); r2, d_contrast = G'(r), dd_contrast = G''(r) (NULL: zero) and the outputs (B,N,T);
+ * psi may be NULL (FasterIVA needs none).  The closures of the reference run on the host on the norms; this is
+ * the arithmetic around them.   replaces: ssspy/bss/iva.py:1187-1188, :1196, :1390-1391. */
+int ssspy_fast_iva_weights(const double *r2, const double *d_contrast, const double *dd_contrast,
+                           double *phi, double *psi, int B, int N, int T, int floor_kind,
+                           double floor_eps, void *stream);
+
+/* One pass over Z with y = W z formed in registers: c[b,i,n,m] = sum_j phi_nj conj(y_inj) z_imj
+ * (B,F,N,N), b[b,i,n] = sum_j psi_nj |y_inj|^2 and a[b,i,n] = sum_j phi_nj (both (B,F,N), a the same
+ * for every bin).  mean_j phi_nj y*_inj z_ij = U_in w_in, so these three
+ * moments stand for the N weighted covariances per bin.
+ * replaces: the (N,N,F,T) broadcasts and means of ssspy/bss/iva.py:1190-1198. */
+int ssspy_fast_iva_stats(const void *Z, const void *W, const double *phi, const double *psi,
+                         void *c, double *b, double *a, int B, int N, int F, int T, void *stream);
+
+/* The FastIVA update from the moments, in place: row n of W_i <- ((a_n - b_in) / T) w_in -
+ * conj(c_in) / T, then ssspy_orthonormalize_rows.   replaces: ssspy/bss/iva.py:1200-1207. */
+int ssspy_fast_iva_step(void *W, const void *c, const double *b, const double *a, int B, int F,
+                        int N, int T, int *info, void *stream);
+
+/* The FasterIVA update, in place: row n of W_i <- conj of the eigenvector of the largest eigenvalue of
+ * U[b,i,n] (B,F,N,N,N) = ssspy_weighted_covariance(Z, phi, SSSPY_WEIGHT_FRAME, S = N), then
+ * ssspy_orthonormalize_rows.  The eigenvector's phase is the decomposition's (as with LAPACK,
+ * arbitrary): a unit factor on row n that the algorithm is blind to.
+ * replaces: ssspy/bss/iva.py:1395-1400. */
+int ssspy_faster_iva_step(void *W, const void *U, int B, int F, int N, int *info, void *stream);
+
+/* W_i <- (W_i W_i^H)^-1/2 W_i in place: u v^H of the singular value decomposition W = u s v^H.  A
+ * Hermitian eigen-decomposition of W W^H and one Newton-Schulz step V <- V - (V V^H - I) V / 2 (forming
+ * W W^H squares the conditioning of W).  A
+ * W W^H whose smallest eigenvalue is not above 1e-14 of the largest, or that is not finite, bumps
+ * info[0] -- the reference's np.linalg.svd never raises and returns some unitary matrix there.
+ * replaces: ssspy/bss/iva.py:1204-1205, :1397-1398. */
+int ssspy_orthonormalize_rows(void *W, int B, int F, int N, int *info, void *stream);
+
+/* P (B,F,N,N) from the covariances C (B,F,N,N) = V Lambda V^H (eigenvalues ascending):
+ * mode 0: Lambda^-1/2 V^H (whiten); mode 1: V^H (pca, ascend=False); mode 2: V^H with the rows in
+ * descending order of the eigenvalues (pca, ascend=True).  The transform is ssspy_separate(X, P).  A
+ * non-finite eigenvalue, or with mode 0 one that is not positive, bumps info[0] (the reference
+ * returns inf / nan).   replaces: ssspy/transform/whiten.py:51-86, ssspy/transform/pca.py:55-88. */
+int ssspy_whitening_filter(const void *C, void *P, int B, int F, int N, int mode, int *info,
+                           void *stream);
 
 /* ------------------------------------------------------------------ cACGMM */
 

@@ -46,6 +46,7 @@ def _units():
         ("ilrma_api.hip", "ilrma_api.o", []),
         ("iva_kernels.hip", "iva_kernels.o", []),
         ("grad_iva.hip", "grad_iva.o", []),
+        ("fast_iva.hip", "fast_iva.o", []),
         ("cacgmm.hip", "cacgmm.o", []),
         ("iss_fused.hip", "iss_fused.o", []),
         ("linalg_kernels.hip", "linalg_kernels.o", []),

@@ -20,6 +20,9 @@ SOURCE_GAUSS, SOURCE_T, SOURCE_GGD = 0, 1, 2
 PARTITION_LATENT, PARTITION_BASIS, PARTITION_ACTIVATION = 1, 2, 4
 SOURCE_ME = 0x100  # OR-ed into the model: source_algorithm="ME"
 CONTRAST_LAPLACE, CONTRAST_GAUSS, CONTRAST_GAUSS_FIXED = 0, 1, 2
+# `mode` of ssspy_whitening_filter, named after what pca() asks for: the first principal component
+# (largest eigenvalue) in the last channel (ascend=False) or in the first (ascend=True)
+WHITEN, PCA_FIRST_COMPONENT_LAST, PCA_FIRST_COMPONENT_FIRST = 0, 1, 2
 # SSSPY_ROUTE_*: what ssspy_ilrma_route returns
 (ROUTE_LATENCY, ROUTE_THROUGHPUT, ROUTE_GROUPED, ROUTE_GENERIC, ROUTE_WIDE_BASIS,
  ROUTE_RUNTIME_N) = range(6)
@@ -42,7 +45,7 @@ MAX_PAIRS = 32
 # the shared operators, ILRMA, AuxIVA, FastGaussMNMF's channels and sources, GaussMNMF's sources),
 # SSSPY_MAX_BASIS
 MAX_SOURCES, RT_MAX_SOURCES, MAX_BASIS = 8, 16, 65536
-ABI_VERSION = 6  # SSSPY_ABI_VERSION of the include/ssspy_amd.h these prototypes mirror
+ABI_VERSION = 7  # SSSPY_ABI_VERSION of the include/ssspy_amd.h these prototypes mirror
 
 _p, _i, _d, _z = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_size_t
 _q = ctypes.c_longlong
@@ -129,6 +132,12 @@ PROTOTYPES = {
     "ssspy_iva_score_weight": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _d, _p]),
     "ssspy_iva_grad_step_logdet_slots": (_i, [_i, _i, _i]),
     "ssspy_iva_grad_step": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _d, _p, _p, _q, _p]),
+    "ssspy_fast_iva_weights": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _d, _p]),
+    "ssspy_fast_iva_stats": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "ssspy_fast_iva_step": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p]),
+    "ssspy_faster_iva_step": (_i, [_p, _p, _i, _i, _i, _p, _p]),
+    "ssspy_orthonormalize_rows": (_i, [_p, _i, _i, _i, _p, _p]),
+    "ssspy_whitening_filter": (_i, [_p, _p, _i, _i, _i, _i, _p, _p]),
     "ssspy_cacgmm_unit_input": (_i, [_p, _p, _i, _i, _i, _i, _i, _d, _p]),
     "ssspy_cacgmm_prepare": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p]),
     "ssspy_cacgmm_frame_pass": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _d, _p, _p, _p, _p, _p,

@@ -722,6 +722,78 @@ def iva_grad_step(W, stats, natural, holonomic, step_size, info, logdet=None, lo
     return W
 
 
+# --------------------------------------------------------------- FastIVA / FasterIVA, whitening
+def fast_iva_weights(r2, d_contrast, dd_contrast, flooring, want_psi=True):
+    """(phi, psi) (B, N, T) from the frame powers and the closures' values on the norms; psi None
+    unless ``want_psi``."""
+    B, N, T = r2.shape
+    phi = dv.empty((B, N, T), dv.f64, r2.device)
+    psi = dv.empty((B, N, T), dv.f64, r2.device) if want_psi else None
+    _lib.check(_L().ssspy_fast_iva_weights(ptr(r2), ptr(d_contrast), ptr(dd_contrast), ptr(phi),
+                                           ptr(psi), B, N, T, flooring[0], flooring[1], _st()),
+               "fast_iva_weights")
+    return phi, psi
+
+
+def fast_iva_stats(Z, W, phi, psi):
+    """(c (B, F, N, N), b (B, F, N), a (B, F, N)): the moments of the FastIVA update, one pass over Z."""
+    B, N, F, T = Z.shape
+    c = dv.empty((B, F, N, N), dv.c128, Z.device)
+    b = dv.empty((B, F, N), dv.f64, Z.device)
+    a = dv.empty((B, F, N), dv.f64, Z.device)
+    _lib.check(_L().ssspy_fast_iva_stats(ptr(Z), ptr(W), ptr(phi), ptr(psi), ptr(c), ptr(b), ptr(a),
+                                         B, N, F, T, _st()), "fast_iva_stats")
+    return c, b, a
+
+
+def fast_iva_step(W, c, b, a, n_frames, info=None):
+    B, F, N, _ = W.shape
+    _lib.check(_L().ssspy_fast_iva_step(ptr(W), ptr(c), ptr(b), ptr(a), B, F, N, int(n_frames),
+                                        ptr(info), _st()), "fast_iva_step")
+    return W
+
+
+def faster_iva_step(W, U, info=None):
+    B, F, N, _ = W.shape
+    assert tuple(U.shape) == (B, F, N, N, N)
+    _lib.check(_L().ssspy_faster_iva_step(ptr(W), ptr(U), B, F, N, ptr(info), _st()),
+               "faster_iva_step")
+    return W
+
+
+def orthonormalize_rows(W, info=None):
+    """W <- (W W^H)^-1/2 W per bin, in place; (B, F, N, N)."""
+    B, F, N, _ = W.shape
+    _lib.check(_L().ssspy_orthonormalize_rows(ptr(W), B, F, N, ptr(info), _st()),
+               "orthonormalize_rows")
+    return W
+
+
+def whitening_filter(C, mode=_lib.WHITEN, info=None, out=None):
+    """P (B, F, N, N) with ssspy_separate(X, P) the whitened / PCA-rotated X; C (B, F, N, N)."""
+    B, F, N, _ = C.shape
+    if out is None:
+        out = dv.empty((B, F, N, N), dv.c128, C.device)
+    _lib.check(_L().ssspy_whitening_filter(ptr(C), ptr(out), B, F, N, int(mode), ptr(info), _st()),
+               "whitening_filter")
+    return out
+
+
+def whitened(X, info=None):
+    """Z (B, N, F, T) = P X with mean_j z z^H = I per bin.  The filter from the eigen-decomposition of
+    C = mean_j x x^H leaves mean_j z z^H = I only to eps cond(C) (the rounding of C itself, seen
+    through Lambda^-1/2), so one correction follows: the covariance D of the first Z, which is
+    well conditioned, and P <- D^-1/2 P with the Hermitian inverse square root -- it rotates
+    nothing, so the rows keep the eigenvectors' order and phase."""
+    B, N, F, T = X.shape
+    C = weighted_covariance(X).reshape(B, F, N, N)
+    P = whitening_filter(C, _lib.WHITEN, info)
+    D = weighted_covariance(separate(X, P)).reshape(B, F, N, N)
+    R = dv.empty((B, F, N, N), dv.c128, X.device)
+    _lib.check(_L().ssspy_sqrtmh(ptr(D), ptr(R), B * F, N, 1, _lib.FLOOR_NONE, 0.0, _st()), "sqrtmh")
+    return separate(X, compose_filters(R, P, D))
+
+
 # ----------------------------------------------------------------------------- FastMNMF
 def fastmnmf_workspace(B, N, M, F, T, K, dev):
     return _workspace(_L().ssspy_fastmnmf_workspace_bytes(B, N, M, F, T, K), dev)

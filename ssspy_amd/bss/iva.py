@@ -16,7 +16,10 @@ The gradient family (ssspy/bss/iva.py:284-406, :644-988, :2341-2973): ``GradIVA`
 one real weight per (source, frame) times the estimate, so an iteration is the two read-only passes
 over the mixture of AuxIVA-IP1 and a per-bin step (csrc/grad_iva.hip); the two generic classes
 take Python closures on the whole estimate and run a compatibility path (see ``GradIVABase``).
-The Fast / Faster / PDS / ADMM IVA variants are out of scope.
+
+The fixed-point family (ssspy/bss/iva.py:409-550, :991-1400): ``FastIVA`` and ``FasterIVA`` on the
+whitened mixture with unitary filters (csrc/fast_iva.hip, see ``FastIVABase``).
+The PDS / ADMM IVA variants are out of scope.
 """
 
 import functools
@@ -35,8 +38,11 @@ from .base import IterativeMethodBase
 
 __all__ = [
     "GradIVABase",
+    "FastIVABase",
     "GradIVA",
     "NaturalGradIVA",
+    "FastIVA",
+    "FasterIVA",
     "AuxIVA",
     "GradLaplaceIVA",
     "GradGaussIVA",
@@ -646,6 +652,267 @@ class AuxGaussIVA(AuxIVA):
         """ref: ssspy/bss/iva.py:3319-3337 (variance refresh) + :3339-3463 (pairs, fixed variance)."""
         self.update_source_model()
         super().update_once_ip2(flooring_fn=flooring_fn)
+
+
+# ------------------------------------------------------------------ fixed point (Fast / Faster)
+class FastIVABase(IVABase):
+    """IVA by fixed-point iterations on the whitened mixture (ref: ssspy/bss/iva.py:409-550).
+
+    ``_reset`` whitens the input once (covariance pass, per-bin filter, one correction of it,
+    ``separate``; all on the device) into ``whitened_input``; ``demix_filter`` acts on that, not on ``input``, and stays
+    unitary, so the loss has no log-determinant term.  ``whitened_input`` and ``demix_filter`` are
+    defined up to a unit factor per (channel, bin): the phase of the eigenvectors is the
+    decomposition's (the reference's is LAPACK's, just as arbitrary).
+
+    The reference has no named Fast classes, so the contrast is always a set of Python closures:
+    ``d_contrast_fn`` / ``dd_contrast_fn`` run on the host on the (n_sources, n_frames) frame norms
+    between the two device passes of an iteration (a few KB down, a few KB up per mixture), and
+    ``contrast_fn`` takes the whole estimate, so a host copy of it is formed whenever the loss is
+    recorded (``record_loss=True``: once per iteration) -- the price of opaque callables.  The three
+    built-in floors run inside the weight kernel; any other flooring callable runs on the host on
+    the norms.
+
+    Where the reference's ``np.linalg.svd`` never raises, a bin whose W W^H is singular to working
+    precision (an injected singular ``demix_filter``) raises ``numpy.linalg.LinAlgError``.
+    """
+
+    whitened_input = Synced(dv.c128)
+
+    def __init__(
+        self,
+        flooring_fn: Optional[Callable[[np.ndarray], np.ndarray]] = functools.partial(
+            max_flooring, eps=EPS
+        ),
+        callbacks: Optional[
+            Union[Callable[["IVABase"], None], List[Callable[["IVABase"], None]]]
+        ] = None,
+        scale_restoration: Union[bool, str] = True,
+        record_loss: bool = True,
+        reference_id: int = 0,
+    ) -> None:
+        super().__init__(
+            flooring_fn=flooring_fn,
+            callbacks=callbacks,
+            scale_restoration=scale_restoration,
+            record_loss=record_loss,
+            reference_id=reference_id,
+        )
+
+    def __call__(
+        self, input: np.ndarray, n_iter: int = 100, initial_call: bool = True, **kwargs
+    ) -> np.ndarray:
+        """Separate a frequency-domain multichannel mixture (ref: ssspy/bss/iva.py:1102-1136)."""
+        self._bind_input(input)
+        self._reset(**kwargs)
+        IterativeMethodBase.__call__(self, n_iter=n_iter, initial_call=initial_call)
+        if self.scale_restoration:
+            self.restore_scale()
+        self._state_set_dev("output", _ops.separate(self._state_dev("whitened_input"),
+                                                    self._state_dev("demix_filter")))
+        return self._final_output()
+
+    def __repr__(self) -> str:
+        s = "FastIVA(scale_restoration={}, record_loss={}".format(
+            self.scale_restoration, self.record_loss
+        )
+        if self.scale_restoration:
+            s += ", reference_id={}".format(self.reference_id)
+        return s + ")"
+
+    def _reset(self, **kwargs) -> None:
+        """ref: ssspy/bss/iva.py:466-476."""
+        assert self._has_input(), "Specify data!"
+        n_sources = self._X.shape[1]
+        if not 2 <= n_sources <= _lib.RT_MAX_SOURCES:
+            raise NotImplementedError(
+                "{} takes 2 to {} sources, got {}.".format(
+                    type(self).__name__, _lib.RT_MAX_SOURCES, n_sources))
+        super()._reset(**kwargs)
+        Z = _ops.whitened(self._X, self._info_tensor())
+        self._state_set_dev("whitened_input", Z)
+        self._state_set_dev("output", _ops.separate(Z, self._state_dev("demix_filter")))
+
+    def separate(
+        self, input: np.ndarray, demix_filter: np.ndarray, use_whitening: bool = True
+    ) -> np.ndarray:
+        """y_ij = W_i z_ij with z the whitened ``input``, or ``input`` itself
+        (ref: ssspy/bss/iva.py:478-509)."""
+        if use_whitening:
+            from ..transform import whiten
+
+            whitened_input = whiten(input)
+        else:
+            whitened_input = input
+        return super().separate(whitened_input, demix_filter=demix_filter)
+
+    def _norm_weights(self, flooring_fn, want_psi: bool):
+        """(phi, psi) (B, N, T) on the device: the frame-power pass, the closures on the host on the
+        norms, the floor in the weight kernel or, for a callable it cannot run, on the host too
+        (ref: ssspy/bss/iva.py:1187-1188, :1196, :1390-1391)."""
+        r2 = _ops.iva_frame_power(self._state_dev("whitened_input"), self._state_dev("demix_filter"))
+        floor = self._resolve_floor(flooring_fn)
+        self._check_device_errors()
+        norm = np.sqrt(dv.to_host(r2))  # (B, N, T)
+
+        def on_norms(fn):
+            out = np.stack([np.asarray(fn(rb), dtype=np.float64) for rb in norm])
+            if out.shape != norm.shape:
+                raise ValueError(
+                    "the contrast derivatives must map (n_sources, n_frames) to the same shape.")
+            return out
+
+        d = on_norms(self.d_contrast_fn)
+        dd = on_norms(self.dd_contrast_fn) if want_psi else None
+        if host_floor(floor) is not None:
+            denom = on_norms(lambda rb: host_floor(floor)(2 * rb))
+            phi = d / denom
+            psi = (2 * phi - dd) / denom if want_psi else None
+            up = functools.partial(dv.to_device, dtype=np.float64, dev=r2.device)
+            return up(phi), (up(psi) if want_psi else None)
+        up = functools.partial(dv.to_device, dtype=np.float64, dev=r2.device)
+        return _ops.fast_iva_weights(r2, up(d), up(dd) if want_psi else None, floor,
+                                     want_psi=want_psi)
+
+    def compute_loss(self) -> float:
+        """sum_n mean_j G(y)_nj; no log-determinant, the filters are unitary
+        (ref: ssspy/bss/iva.py:511-531)."""
+        Y = dv.to_host(_ops.separate(self._state_dev("whitened_input"),
+                                     self._state_dev("demix_filter")))
+        self._check_device_errors()
+        values = np.array([np.sum(np.mean(self.contrast_fn(Yb), axis=1), axis=0) for Yb in Y],
+                          dtype=np.float64)
+        return self._loss_entry(values)
+
+    def apply_projection_back(self) -> None:
+        """The estimate scaled against the unwhitened input, the filters re-fitted on the whitened
+        one as Y Z^H (Z Z^H)^-1 (ref: ssspy/bss/iva.py:533-550)."""
+        assert self.scale_restoration, "Set self.scale_restoration=True."
+        Z = self._state_dev("whitened_input")
+        Y = _ops.separate(Z, self._state_dev("demix_filter"))
+        G = _ops.projection_back_scale(_ops.cross_covariance(self._X, Y),
+                                       _ops.cross_covariance(Y, Y), self.reference_id,
+                                       self._info_tensor())
+        _ops.separate(Y, G, out=Y)
+        W = _ops.demix_from_covariance(_ops.cross_covariance(Y, Z), _ops.cross_covariance(Z, Z),
+                                       self._info_tensor())
+        self._state_set_dev("demix_filter", W)
+        self._state_set_dev("output", Y)
+
+    def apply_minimal_distortion_principle(self) -> None:
+        """As the reference does it (IVABase's method, whose ``separate`` call whitens;
+        ssspy/bss/iva.py:269-281): the estimate W z scaled against the unwhitened input, the filters
+        re-fitted on the UNWHITENED input as Y X^H (X X^H)^-1 -- ``__call__`` then applies them to
+        the whitened one (:1132-1134)."""
+        assert self.scale_restoration, "Set self.scale_restoration=True."
+        Y = _ops.separate(self._state_dev("whitened_input"), self._state_dev("demix_filter"))
+        G = _ops.mdp_scale(_ops.cross_covariance(Y, self._X), _ops.cross_covariance(Y, Y),
+                           self.reference_id)
+        _ops.separate(Y, G, out=Y)
+        W = _ops.demix_from_covariance(_ops.cross_covariance(Y, self._X), self._C(),
+                                       self._info_tensor())
+        self._state_set_dev("demix_filter", W)
+        self._state_set_dev("output", Y)
+
+
+class FastIVA(FastIVABase):
+    """Fast independent vector analysis (ref: ssspy/bss/iva.py:991-1207).
+
+    An iteration reads the whitened mixture twice: the frame-power pass, and one pass that leaves the
+    three moments per (bin, source) the update needs (``_ops.fast_iva_stats``); the per-bin step forms
+    the new filters and orthonormalises their rows.  Host costs: see ``FastIVABase``."""
+
+    def __init__(
+        self,
+        contrast_fn: Callable[[np.ndarray], np.ndarray] = None,
+        d_contrast_fn: Callable[[np.ndarray], np.ndarray] = None,
+        dd_contrast_fn: Callable[[np.ndarray], np.ndarray] = None,
+        flooring_fn: Optional[Callable[[np.ndarray], np.ndarray]] = functools.partial(
+            max_flooring, eps=EPS
+        ),
+        callbacks: Optional[
+            Union[Callable[["FastIVA"], None], List[Callable[["FastIVA"], None]]]
+        ] = None,
+        scale_restoration: Union[bool, str] = True,
+        record_loss: bool = True,
+        reference_id: int = 0,
+    ) -> None:
+        super().__init__(
+            flooring_fn=flooring_fn,
+            callbacks=callbacks,
+            scale_restoration=scale_restoration,
+            record_loss=record_loss,
+            reference_id=reference_id,
+        )
+        if contrast_fn is None:
+            raise ValueError("Specify contrast function.")
+        self.contrast_fn = contrast_fn
+        if d_contrast_fn is None:
+            raise ValueError("Specify derivative of contrast function.")
+        self.d_contrast_fn = d_contrast_fn
+        if dd_contrast_fn is None:
+            raise ValueError("Specify second order derivative of contrast function.")
+        self.dd_contrast_fn = dd_contrast_fn
+
+    def update_once(
+        self,
+        flooring_fn: Optional[Union[str, Callable[[np.ndarray], np.ndarray]]] = "self",
+    ) -> None:
+        """ref: ssspy/bss/iva.py:1150-1207."""
+        Z, W = self._state_dev("whitened_input"), self._state_dev("demix_filter")
+        phi, psi = self._norm_weights(flooring_fn, want_psi=True)
+        c, b, a = _ops.fast_iva_stats(Z, W, phi, psi)
+        _ops.fast_iva_step(W, c, b, a, self.n_frames, self._info_tensor())
+        self._state_touch("demix_filter")
+
+
+class FasterIVA(FastIVABase):
+    """Faster independent vector analysis (ref: ssspy/bss/iva.py:1210-1400).
+
+    An iteration is the frame-power pass, the frame-weighted covariance pass of AuxIVA-IP1 on the
+    whitened mixture and a per-bin step: the principal eigenvector of every U_in into row n, then
+    the row orthonormalisation.  Host costs: see ``FastIVABase``."""
+
+    def __init__(
+        self,
+        contrast_fn: Callable[[np.ndarray], np.ndarray] = None,
+        d_contrast_fn: Callable[[np.ndarray], np.ndarray] = None,
+        flooring_fn: Optional[Callable[[np.ndarray], np.ndarray]] = functools.partial(
+            max_flooring, eps=EPS
+        ),
+        callbacks: Optional[
+            Union[Callable[["FasterIVA"], None], List[Callable[["FasterIVA"], None]]]
+        ] = None,
+        scale_restoration: Union[bool, str] = True,
+        record_loss: bool = True,
+        reference_id: int = 0,
+    ) -> None:
+        super().__init__(
+            flooring_fn=flooring_fn,
+            callbacks=callbacks,
+            scale_restoration=scale_restoration,
+            record_loss=record_loss,
+            reference_id=reference_id,
+        )
+        if contrast_fn is None:
+            raise ValueError("Specify contrast function.")
+        self.contrast_fn = contrast_fn
+        if d_contrast_fn is None:
+            raise ValueError("Specify derivative of contrast function.")
+        self.d_contrast_fn = d_contrast_fn
+
+    def __repr__(self) -> str:
+        return "FasterIVA" + super().__repr__()[len("FastIVA"):]
+
+    def update_once(
+        self,
+        flooring_fn: Optional[Union[str, Callable[[np.ndarray], np.ndarray]]] = "self",
+    ) -> None:
+        """ref: ssspy/bss/iva.py:1354-1400."""
+        Z, W = self._state_dev("whitened_input"), self._state_dev("demix_filter")
+        phi, _ = self._norm_weights(flooring_fn, want_psi=False)
+        U = _ops.weighted_covariance(Z, phi, _lib.WEIGHT_FRAME, self.n_sources)
+        _ops.faster_iva_step(W, U, self._info_tensor())
+        self._state_touch("demix_filter")
 
 
 # ------------------------------------------------------------------ gradient / natural gradient

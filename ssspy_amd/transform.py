@@ -12,6 +12,10 @@ output to ``istft`` without the spectrogram crossing PCIe.  ``n_fft``: a power o
 length in [2, 32768] (Bluestein; up to 8192 points in LDS, longer transforms on a workspace in HBM);
 ``window``: an array, or what ``scipy.signal.get_window`` takes for
 its periodic windows (a name, or a ``(name, parameter)`` tuple).
+
+``whiten`` and ``pca`` (ssspy/transform/whiten.py, ssspy/transform/pca.py) are here as well: complex
+spectrograms go through the covariance pass, the per-bin whitening / PCA filter and ``separate`` on
+the device; the real time-domain forms are one small matrix per signal and stay NumPy on the host.
 """
 
 import warnings
@@ -21,7 +25,6 @@ import numpy as np
 
 from . import _device as dv
 from . import _lib
-
 
 
 def _L():
@@ -202,3 +205,87 @@ def istft(Z, n_fft: int, hop_length: Optional[int] = None, window="hann", device
     )
     x = x.reshape(lead + (L,))
     return x if device_output else dv.to_host(x)
+
+
+def _device_rotation(input: np.ndarray, mode: int, what: str) -> np.ndarray:
+    """P x per bin with P from the eigen-decomposition of mean_j x x^H; complex (M, F, T) or
+    (B, M, F, T).  A covariance the filter kernel cannot decompose raises LinAlgError, where the
+    reference returns inf / nan."""
+    from . import _ops
+
+    batched = input.ndim == 4
+    n_channels = input.shape[1 if batched else 0]
+    if not 2 <= n_channels <= _lib.RT_MAX_SOURCES:
+        raise NotImplementedError(
+            "{} takes 2 to {} channels, got {}.".format(what, _lib.RT_MAX_SOURCES, n_channels))
+    X = dv.to_device(input if batched else input[None], dtype=np.complex128)
+    B, M, F, T = X.shape
+    info = dv.zeros((1,), dv.i32, X.device)
+    if mode == _lib.WHITEN:
+        out = dv.to_host(_ops.whitened(X, info))
+    else:
+        C = _ops.weighted_covariance(X).reshape(B, F, M, M)
+        out = dv.to_host(_ops.separate(X, _ops.whitening_filter(C, mode, info)))
+    _lib.raise_if_singular(int(info.item()), what)
+    return out if batched else out[0]
+
+
+def whiten(input: np.ndarray) -> np.ndarray:
+    """Whitening (sphering): z = Lambda^-1/2 V^H x with mean_j x x^H = V Lambda V^H
+    (ref: ssspy/transform/whiten.py:4-94).
+
+    Complex (n_channels, n_bins, n_frames) and (batch_size, n_channels, n_bins, n_frames) inputs run
+    on the device; real (n_channels, n_samples) and (batch_size, n_channels, n_samples) inputs are
+    one n_channels x n_channels problem per signal and stay NumPy on the host.  The eigenvectors
+    carry the decomposition's phase (with LAPACK as here, arbitrary): the rows of the complex result
+    are defined up to a unit factor per (channel, bin).
+    """
+    if input.ndim == 2:
+        if np.iscomplexobj(input):
+            raise ValueError("Real tensor is expected, but given complex tensor.")
+        return _host_rotation(input[np.newaxis], scale=True, reverse=False)[0]
+    elif input.ndim == 3:
+        if np.iscomplexobj(input):
+            return _device_rotation(input, _lib.WHITEN, "whiten")
+        return _host_rotation(input, scale=True, reverse=False)
+    elif input.ndim == 4:
+        if np.iscomplexobj(input):
+            return _device_rotation(input, _lib.WHITEN, "whiten")
+        raise ValueError("Complex tensor is expected, but given real tensor.")
+    raise ValueError(
+        "The dimension of input is expected 2, 3, or 4, but given {}.".format(input.ndim)
+    )
+
+
+def pca(input: np.ndarray, ascend: bool = True) -> np.ndarray:
+    """Principal component analysis: y = V^H x, the first channel the first principal component when
+    ``ascend`` (ref: ssspy/transform/pca.py:4-96).  Where it runs: as for ``whiten``."""
+    if input.ndim == 2:
+        if np.iscomplexobj(input):
+            raise ValueError("Real tensor is expected, but given complex tensor.")
+        return _host_rotation(input[np.newaxis], scale=False, reverse=bool(ascend))[0]
+    elif input.ndim == 3:
+        if np.iscomplexobj(input):
+            return _device_rotation(input, _lib.PCA_FIRST_COMPONENT_FIRST if ascend else _lib.PCA_FIRST_COMPONENT_LAST,
+                                    "pca")
+        return _host_rotation(input, scale=False, reverse=bool(ascend))
+    elif input.ndim == 4:
+        if np.iscomplexobj(input):
+            return _device_rotation(input, _lib.PCA_FIRST_COMPONENT_FIRST if ascend else _lib.PCA_FIRST_COMPONENT_LAST,
+                                    "pca")
+        raise ValueError("Complex tensor is expected, but given real tensor.")
+    raise ValueError(
+        "The dimension of input is expected 3 or 4, but given {}.".format(input.ndim)
+    )
+
+
+def _host_rotation(x: np.ndarray, scale: bool, reverse: bool) -> np.ndarray:
+    """Real time-domain signals (batch_size, n_channels, n_samples) on the host."""
+    covariance = np.einsum("bmt,bnt->bmn", x, x) / x.shape[-1]
+    lam, V = np.linalg.eigh(covariance)
+    if reverse:
+        V = V[..., ::-1]
+    P = V.transpose(0, 2, 1)
+    if scale:
+        P = (1 / np.sqrt(lam))[:, :, np.newaxis] * P
+    return P @ x
