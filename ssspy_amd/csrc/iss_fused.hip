@@ -401,7 +401,10 @@ static int iss1_fused_impl(void *Y, const double *weight, int weight_kind, doubl
   SSSPY_REQUIRE(Y && weight && B > 0 && F > 0 && T > 0, "iss1_fused: bad argument");
   SSSPY_REQUIRE(weight_kind == SSSPY_WEIGHT_FRAME || weight_kind == SSSPY_WEIGHT_BIN_FRAME,
                 "iss1_fused: weight_kind must be FRAME or BIN_FRAME");
-  SSSPY_REQUIRE(T <= ssspy_iss1_fused_max_frames(N), "iss1_fused: n_frames above the fused limit");
+  // (a well-formed call the register-resident slab cannot hold: UNSUPPORTED, as the dispatch below
+  //  answers for a frame count it has no instance for -- not a bad argument)
+  if (N >= 1 && N <= SSSPY_MAX_SOURCES && T > ssspy_iss1_fused_max_frames(N))
+    return fail(SSSPY_ERR_UNSUPPORTED, "iss1_fused: n_frames above the fused limit");
   size_t scratch_off = 0;
   const size_t r2_bytes = iss_r2_layout(B, N, F, T, &scratch_off);
   const size_t need = r2_bytes + iss_logdet_slots_bytes(B, F);
