@@ -96,8 +96,9 @@ const char *ssspy_amd_version(void);
  * 4: the ssspy_cacgmm_* entry points added.
  * 5: ssspy_fastmnmf_route added (additive: no existing argument list changed).
  * 6: ssspy_gmnmf_route added (additive).
- * 7: the FastIVA / FasterIVA entry points and ssspy_whitening_filter added (additive). */
-#define SSSPY_ABI_VERSION 7
+ * 7: the FastIVA / FasterIVA entry points and ssspy_whitening_filter added (additive).
+ * 8: the IPSDTA entry points and ssspy_matmul3 added (additive). */
+#define SSSPY_ABI_VERSION 8
 int ssspy_abi_version(void);
 const char *ssspy_last_error(void);
 
@@ -1058,6 +1059,65 @@ int ssspy_lqpqm2(const void *H, const void *v, const double *z, void *y, long lo
 int ssspy_lqpqm2_masked(const void *H, const void *v, const double *z, void *y, long long n, int L,
                         int max_iter, int floor_kind, double floor_eps, void *newton_ws,
                         int *not_converged, const int *singular, void *stream);
+
+/* ------------------------------------------------------------------ IPSDTA (block decomposition)
+ * GaussIPSDTA / TIPSDTA with the MM source model and the VCD spatial model (ssspy/bss/ipsdta.py).
+ * The F bins are cut into n_blocks blocks; a launch covers one partition of equal block size L
+ * (the reference's "low" blocks of size F / n_blocks and its "high" blocks of one more,
+ * ipsdta.py:545-556): n_part_blocks blocks from bin first_bin on, numbered from first_block among
+ * all n_blocks.  2 <= N <= 8, 1 <= L <= 8, 1 <= K <= 32.
+ * X (B, N, F, T), W (B, F, N, N), basis (B, N, K, n_part_blocks, L, L) c128; activation (B, N, K, T),
+ * pi (B, N, T) f64 or NULL (weight 1: the Gaussian model).
+ * Per (mixture, source, block, frame): y = W x on the block's bins, R = to_psd(sum_k v T) with
+ * to_psd's default floor (max-flooring of the eigenvalues at 1e-10; ipsdta.py:643-647), R^-1,
+ * u = R^-1 y.  `mode` selects what leaves the pass:
+ *   SSSPY_IPSDTA_QUAD  out0 = Re(y^H R^-1 y), out1 = log det R, both (B, N, n_blocks, T) f64
+ *                      (ipsdta.py:1174-1181, :1438-1446)
+ *   SSSPY_IPSDTA_BASIS out0 = P = mean_t v R^-1, out1 = Q = mean_t v pi u u^H, both shaped as basis
+ *                      (ipsdta.py:926-939, :1469-1483)
+ *   SSSPY_IPSDTA_ACT   out0 = pi Re(u^H T_k u), out1 = Re tr(R^-1 T_k), both (B, N, K, n_blocks, T)
+ *                      f64: the terms of ipsdta.py:1001-1004, :1586-1589 before the sum over blocks
+ *   SSSPY_IPSDTA_COV   out0 (B, n_part_blocks, L, L, N, N, N) c128 = mean_t pi R^-1[b][a] x_a x_b^H,
+ *                      the weighted covariance of the VCD sweep (ipsdta.py:1096-1102, :1711-1718);
+ *                      out1 unused
+ * route: NULL, or (B, N, n_blocks, T) int32: 1 where the matrix took the eigenvalue route of to_psd
+ * (0: a Cholesky factorisation of R - 1e-10 I proved the floor idle). */
+enum { SSSPY_IPSDTA_QUAD = 0, SSSPY_IPSDTA_BASIS = 1, SSSPY_IPSDTA_ACT = 2, SSSPY_IPSDTA_COV = 3 };
+int ssspy_ipsdta_frame_pass(const void *X, const void *W, const void *basis, const double *activation,
+                            const double *pi, int B, int N, int F, int T, int K, int n_part_blocks,
+                            int L, int first_bin, int first_block, int n_blocks, int mode,
+                            void *out0, void *out1, int *route, void *stream);
+
+/* From the QUAD outputs: pi = (dof + 2F) / (dof + 2 sum_blocks max(quad, 0)) (B, N, T) (model
+ * SSSPY_SOURCE_T; ipsdta.py:1518, :1618, :1758; NULL: not wanted) and the data term of the loss (B)
+ * (NULL: not wanted): Gauss mean_t(max(sum quad, 0) per partition + sum log det R)
+ * (ipsdta.py:1177-1184), t mean_t(sum_n (dof + 2F) / 2 log(1 + 2 / dof sum_blocks max(quad, 0)) +
+ * sum log det R) (ipsdta.py:1840-1866).  The first n_low_blocks blocks are the low partition. */
+int ssspy_ipsdta_weight_loss(const double *quad, const double *logdet, int B, int N, int n_blocks,
+                             int n_low_blocks, int T, int F, int model, double dof, double *pi,
+                             double *loss, void *stream);
+
+/* activation (B, N, K, T) *= sqrt(sum_blocks num / sum_blocks den) from the ACT outputs
+ * (ipsdta.py:1027-1033, :1623-1632). */
+int ssspy_ipsdta_activation(double *activation, const double *num, const double *den, int B, int N,
+                            int K, int n_blocks, int T, void *stream);
+
+/* Trace normalisation: T /= tr, V *= tr with tr the trace of a (source, basis)'s matrices summed
+ * over both partitions (ipsdta.py:666-697).  basis_high may be NULL with n_high_blocks == 0. */
+int ssspy_ipsdta_normalize(void *basis_low, void *basis_high, double *activation, int B, int N, int K,
+                           int n_low_blocks, int L_low, int n_high_blocks, int L_high, int T,
+                           void *stream);
+
+/* The VCD sweep of one partition, in place on W (B, F, N, N) (_update_spatial_model.py:516-608):
+ * weighted_covariance (B, n_part_blocks, L, L, N, N, N); the singular branch is taken where
+ * |xi_hat| < threshold (ipsdta.py:1104-1106: flooring_fn(0)).  info[0] counts singular systems. */
+int ssspy_ipsdta_vcd(void *W, const void *weighted_covariance, int B, int F, int N, int n_part_blocks,
+                     int L, int first_bin, double threshold, int *info, void *stream);
+
+/* out = (A B) C for n matrices of size L x L (1..8), none aliasing out: the products of the basis
+ * steps, T Q T (ipsdta.py:940) and Q^1/2 T P T Q^1/2, T Q^1/2 (.) Q^1/2 T (ipsdta.py:1487-1489). */
+int ssspy_matmul3(const void *A, const void *Bm, const void *C, void *out, long long n, int L,
+                  void *stream);
 
 /* ------------------------------------------------------------------ STFT / ISTFT
  * The transforms the reference's workflow takes from SciPy either side of a separator

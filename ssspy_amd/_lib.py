@@ -23,6 +23,9 @@ CONTRAST_LAPLACE, CONTRAST_GAUSS, CONTRAST_GAUSS_FIXED = 0, 1, 2
 # `mode` of ssspy_whitening_filter, named after what pca() asks for: the first principal component
 # (largest eigenvalue) in the last channel (ascend=False) or in the first (ascend=True)
 WHITEN, PCA_FIRST_COMPONENT_LAST, PCA_FIRST_COMPONENT_FIRST = 0, 1, 2
+# SSSPY_IPSDTA_*: `mode` of ssspy_ipsdta_frame_pass; the limits of the IPSDTA kernels
+IPSDTA_QUAD, IPSDTA_BASIS, IPSDTA_ACT, IPSDTA_COV = range(4)
+IPSDTA_MAX_SOURCES, IPSDTA_MAX_BLOCK, IPSDTA_MAX_BASIS = 8, 8, 32
 # SSSPY_ROUTE_*: what ssspy_ilrma_route returns
 (ROUTE_LATENCY, ROUTE_THROUGHPUT, ROUTE_GROUPED, ROUTE_GENERIC, ROUTE_WIDE_BASIS,
  ROUTE_RUNTIME_N) = range(6)
@@ -45,7 +48,7 @@ MAX_PAIRS = 32
 # the shared operators, ILRMA, AuxIVA, FastGaussMNMF's channels and sources, GaussMNMF's sources),
 # SSSPY_MAX_BASIS
 MAX_SOURCES, RT_MAX_SOURCES, MAX_BASIS = 8, 16, 65536
-ABI_VERSION = 7  # SSSPY_ABI_VERSION of the include/ssspy_amd.h these prototypes mirror
+ABI_VERSION = 8  # SSSPY_ABI_VERSION of the include/ssspy_amd.h these prototypes mirror
 
 _p, _i, _d, _z = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_size_t
 _q = ctypes.c_longlong
@@ -138,6 +141,13 @@ PROTOTYPES = {
     "ssspy_faster_iva_step": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "ssspy_orthonormalize_rows": (_i, [_p, _i, _i, _i, _p, _p]),
     "ssspy_whitening_filter": (_i, [_p, _p, _i, _i, _i, _i, _p, _p]),
+    "ssspy_ipsdta_frame_pass": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
+                                     _p, _p, _p, _p]),
+    "ssspy_ipsdta_weight_loss": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _p, _p, _p]),
+    "ssspy_ipsdta_activation": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "ssspy_ipsdta_normalize": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "ssspy_ipsdta_vcd": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _d, _p, _p]),
+    "ssspy_matmul3": (_i, [_p, _p, _p, _p, _q, _i, _p]),
     "ssspy_cacgmm_unit_input": (_i, [_p, _p, _i, _i, _i, _i, _i, _d, _p]),
     "ssspy_cacgmm_prepare": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p]),
     "ssspy_cacgmm_frame_pass": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _d, _p, _p, _p, _p, _p,

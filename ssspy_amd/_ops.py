@@ -1143,3 +1143,122 @@ def cacgmm_separate(posterior, X, reference_id, out=None):
     _lib.check(_L().ssspy_cacgmm_separate(ptr(posterior), ptr(X), ptr(out), B, N, M, F, T,
                                           int(reference_id), _st()), "cacgmm_separate")
     return out
+
+
+# ---- IPSDTA (csrc/ipsdta.hip).  A partition is (basis (B, N, K, Cn, L, L), first bin, first block):
+# the blocks of one size, see ssspy_ipsdta_frame_pass.
+def ipsdta_frame_pass(X, W, part, activation, pi, n_blocks, mode, out0, out1=None, route=None):
+    basis, first_bin, first_block = part
+    B, N, F, T = X.shape
+    K, Cn, L = basis.shape[2], basis.shape[3], basis.shape[4]
+    _lib.check(_L().ssspy_ipsdta_frame_pass(
+        ptr(X), ptr(W), ptr(basis), ptr(activation), ptr(pi), B, N, F, T, K, Cn, L, first_bin,
+        first_block, n_blocks, mode, ptr(out0), ptr(out1), ptr(route), _st()), "ipsdta_frame_pass")
+
+
+def ipsdta_quadratic(X, W, parts, activation, n_blocks, route=None):
+    """(quad, logdet) (B, N, n_blocks, T) over every partition."""
+    B, N, F, T = X.shape
+    quad = dv.empty((B, N, n_blocks, T), dv.f64, X.device)
+    logdet = dv.empty((B, N, n_blocks, T), dv.f64, X.device)
+    for part in parts:
+        ipsdta_frame_pass(X, W, part, activation, None, n_blocks, _lib.IPSDTA_QUAD, quad, logdet,
+                          route)
+    return quad, logdet
+
+
+def ipsdta_weight_loss(quad, logdet, n_low_blocks, n_bins, model, dof, want_pi=False, loss=None):
+    B, N, n_blocks, T = quad.shape
+    pi = dv.empty((B, N, T), dv.f64, quad.device) if want_pi else None
+    _lib.check(_L().ssspy_ipsdta_weight_loss(ptr(quad), ptr(logdet), B, N, n_blocks, n_low_blocks, T,
+                                             n_bins, model, float(dof), ptr(pi), ptr(loss), _st()),
+               "ipsdta_weight_loss")
+    return pi
+
+
+def ipsdta_basis_statistics(X, W, part, activation, pi, n_blocks):
+    """(P, Q), each shaped as the partition's basis."""
+    basis = part[0]
+    P = dv.empty(tuple(basis.shape), dv.c128, X.device)
+    Q = dv.empty(tuple(basis.shape), dv.c128, X.device)
+    ipsdta_frame_pass(X, W, part, activation, pi, n_blocks, _lib.IPSDTA_BASIS, P, Q)
+    return P, Q
+
+
+def ipsdta_activation_terms(X, W, parts, activation, pi, n_blocks):
+    """(num, den) (B, N, K, n_blocks, T): the per-block terms of the activation update."""
+    B, N, F, T = X.shape
+    K = activation.shape[2]
+    num = dv.empty((B, N, K, n_blocks, T), dv.f64, X.device)
+    den = dv.empty((B, N, K, n_blocks, T), dv.f64, X.device)
+    for part in parts:
+        ipsdta_frame_pass(X, W, part, activation, pi, n_blocks, _lib.IPSDTA_ACT, num, den)
+    return num, den
+
+
+def ipsdta_activation(activation, num, den):
+    B, N, K, n_blocks, T = num.shape
+    _lib.check(_L().ssspy_ipsdta_activation(ptr(activation), ptr(num), ptr(den), B, N, K, n_blocks, T,
+                                            _st()), "ipsdta_activation")
+    return activation
+
+
+def ipsdta_weighted_covariance(X, W, part, activation, pi, n_blocks):
+    """(B, Cn, L, L, N, N, N): the weighted covariance of the VCD sweep of one partition."""
+    basis = part[0]
+    B, N = X.shape[0], X.shape[1]
+    Cn, L = basis.shape[3], basis.shape[4]
+    out = dv.empty((B, Cn, L, L, N, N, N), dv.c128, X.device)
+    ipsdta_frame_pass(X, W, part, activation, pi, n_blocks, _lib.IPSDTA_COV, out)
+    return out
+
+
+def ipsdta_normalize(basis_low, basis_high, activation):
+    B, N, K, Clow, Llow = basis_low.shape[:5]
+    Chigh, Lhigh = (basis_high.shape[3], basis_high.shape[4]) if basis_high is not None else (0, 0)
+    _lib.check(_L().ssspy_ipsdta_normalize(ptr(basis_low), ptr(basis_high), ptr(activation), B, N, K,
+                                           Clow, Llow, Chigh, Lhigh, activation.shape[-1], _st()),
+               "ipsdta_normalize")
+
+
+def ipsdta_vcd(W, weighted_covariance, first_bin, threshold, info=None):
+    """The VCD sweep of one partition, in place on W (B, F, N, N)."""
+    B, F, N = W.shape[0], W.shape[1], W.shape[2]
+    Cn, L = weighted_covariance.shape[1], weighted_covariance.shape[2]
+    _lib.check(_L().ssspy_ipsdta_vcd(ptr(W), ptr(weighted_covariance), B, F, N, Cn, L, first_bin,
+                                     float(threshold), ptr(info), _st()), "ipsdta_vcd")
+    return W
+
+
+def matmul3(A, Bm, C):
+    """(A B) C for stacks (..., L, L) of small matrices on the device."""
+    L = A.shape[-1]
+    out = dv.empty(tuple(A.shape), dv.c128, A.device)
+    _lib.check(_L().ssspy_matmul3(ptr(A), ptr(Bm), ptr(C), ptr(out), A.numel() // (L * L), L, _st()),
+               "matmul3")
+    return out
+
+
+def to_psd_dev(A, flooring):
+    """to_psd on a device stack (..., L, L) with one of the kernels' floors (kind, eps)."""
+    L = A.shape[-1]
+    out = dv.empty(tuple(A.shape), dv.c128, A.device)
+    _lib.check(_L().ssspy_to_psd(ptr(A), ptr(out), A.numel() // (L * L), L, flooring[0], flooring[1],
+                                 _st()), "to_psd")
+    return out
+
+
+def sqrtmh_dev(A, inverse=False, flooring=(_lib.FLOOR_NONE, 0.0)):
+    L = A.shape[-1]
+    out = dv.empty(tuple(A.shape), dv.c128, A.device)
+    _lib.check(_L().ssspy_sqrtmh(ptr(A), ptr(out), A.numel() // (L * L), L, int(inverse), flooring[0],
+                                 flooring[1], _st()), "sqrtmh")
+    return out
+
+
+def gmeanmh_dev(A, Bm, type=1):
+    L = A.shape[-1]
+    out = dv.empty(tuple(A.shape), dv.c128, A.device)
+    _lib.check(_L().ssspy_gmeanmh(ptr(A), ptr(Bm), ptr(out), A.numel() // (L * L), L, type, _st()),
+               "gmeanmh")
+    return out

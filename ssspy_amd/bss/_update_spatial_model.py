@@ -184,3 +184,57 @@ def update_by_ipa(
                       UserWarning)
     _lib.raise_if_singular(singular, "update_by_ipa")
     return out
+
+
+def abs_below(threshold: float) -> Callable[[np.ndarray], np.ndarray]:
+    """``lambda x: np.abs(x) < threshold`` in a form the VCD kernel can take: the singular
+    condition IPSDTA hands to ``update_by_block_decomposition_vcd`` (ref: ssspy/bss/ipsdta.py:1105)."""
+    def singular_fn(x):
+        return np.abs(x) < threshold
+
+    singular_fn.threshold = float(threshold)
+    return singular_fn
+
+
+def update_by_block_decomposition_vcd(
+    demix_filter: np.ndarray,
+    weighted_covariance: np.ndarray,
+    singular_fn: Optional[Callable[[np.ndarray], np.ndarray]] = None,
+    overwrite: bool = True,
+) -> np.ndarray:
+    """Update demixing filters by vectorwise coordinate descent on block-decomposed bases
+    (ref: _update_spatial_model.py:516-608).
+
+    Args:
+        demix_filter: (n_blocks, n_neighbors, n_sources, n_channels) complex.
+        weighted_covariance: (n_blocks, n_neighbors, n_neighbors, n_sources, n_channels, n_channels).
+        singular_fn: ``None`` (``x == 0``, as in the reference) or ``abs_below(threshold)``; the
+            condition is decided inside the sweep, so any other callable raises NotImplementedError.
+        overwrite: write the result back into ``demix_filter`` (and return it).
+
+    2 to 8 sources.  Raises numpy.linalg.LinAlgError if one of the per-row systems is singular.
+    """
+    if singular_fn is None:
+        threshold = 5e-324  # |x| < the smallest positive double: x == 0
+    elif hasattr(singular_fn, "threshold"):
+        threshold = float(singular_fn.threshold)
+    else:
+        raise NotImplementedError(
+            "update_by_block_decomposition_vcd takes singular_fn=None or abs_below(threshold): the "
+            "condition is evaluated inside the sweep kernel, got {!r}".format(singular_fn))
+    W = np.asarray(demix_filter)
+    C, L, N, M = W.shape
+    if N != M or not 2 <= N <= _lib.IPSDTA_MAX_SOURCES:
+        raise NotImplementedError("the VCD sweep takes 2 to {} sources (square filters), got {} x {}."
+                                  .format(_lib.IPSDTA_MAX_SOURCES, N, M))
+    dW = dv.to_device(W.reshape(1, C * L, N, N), dtype=np.complex128)
+    dR = dv.to_device(np.asarray(weighted_covariance).reshape(1, C, L, L, N, N, N),
+                      dtype=np.complex128)
+    info = dv.zeros((1,), dv.i32)
+    _ops.ipsdta_vcd(dW, dR, 0, threshold, info)
+    _lib.raise_if_singular(int(info.item()), "update_by_block_decomposition_vcd")
+    out = dv.to_host(dW).reshape(C, L, N, N)
+    if overwrite and isinstance(demix_filter, np.ndarray):
+        demix_filter[...] = out
+        return demix_filter
+    return out
