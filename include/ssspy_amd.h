@@ -97,8 +97,9 @@ const char *ssspy_amd_version(void);
  * 5: ssspy_fastmnmf_route added (additive: no existing argument list changed).
  * 6: ssspy_gmnmf_route added (additive).
  * 7: the FastIVA / FasterIVA entry points and ssspy_whitening_filter added (additive).
- * 8: the IPSDTA entry points and ssspy_matmul3 added (additive). */
-#define SSSPY_ABI_VERSION 8
+ * 8: the IPSDTA entry points and ssspy_matmul3 added (additive).
+ * 9: the FDICA entry points added (additive). */
+#define SSSPY_ABI_VERSION 9
 int ssspy_abi_version(void);
 const char *ssspy_last_error(void);
 
@@ -622,6 +623,55 @@ int ssspy_iva_grad_step_logdet_slots(int B, int F, int N);
 int ssspy_iva_grad_step(void *W, const void *stats, int stats_ready, int B, int F, int N,
                         int natural, int holonomic, double step_size, int *info, double *logdet,
                         long long logdet_stride, void *stream);
+
+/* ------------------------------------------------- FDICA (Laplace model) */
+
+/* `algorithm` of the FDICA entry points */
+enum {
+  SSSPY_FDICA_GRAD = 0,         /* W <- W - step_size D W^-H */
+  SSSPY_FDICA_NATURAL_GRAD = 1, /* W <- W - step_size D W    */
+  SSSPY_FDICA_AUX_IP1 = 2,      /* one iterative-projection sweep */
+  SSSPY_FDICA_AUX_IP2 = 3,      /* pairwise sweep: per-iteration operators only */
+};
+
+/* what the route function returns */
+enum {
+  SSSPY_FDICA_ROUTE_RESIDENT = 0,  /* one launch, the bin's slab of the mixture in LDS          */
+  SSSPY_FDICA_ROUTE_STREAMING = 1, /* the same kernel, the slab re-read from memory every step  */
+  SSSPY_FDICA_ROUTE_COMPOSED = 2,  /* per-iteration operators (separate, weight, covariance...) */
+};
+
+/* The per-element weight of the Laplace model on the estimate Y (B,S,F,T) (all N rows, or the two
+ * rows of an IP2 pair): aux_form == 0 the score weight 1 / floor(|y|) (phi(y) = weight * y),
+ * aux_form != 0 the auxiliary weight 2 / floor(2 |y|); weight (B,S,F,T) f64 (may be NULL when only
+ * the contrast is wanted).  contrast (may be NULL): sum_s mean_j 2 |y_sij| of bin i of mixture b at
+ * contrast[i * contrast_stride + b], to be added over the bins in slot order
+ * (ssspy_fold_scalar_slots with F slots); no atomics.
+ * replaces: ssspy/bss/fdica.py:1109-1112, :1231-1234, :1342, :1354-1355, :1628-1640. */
+int ssspy_fdica_weight(const void *Y, double *weight, int B, int S, int F, int T, int aux_form,
+                       int floor_kind, double floor_eps, double *contrast,
+                       long long contrast_stride, void *stream);
+
+/* Which route a shape takes: the bins of FDICA are independent, so a workgroup can own one
+ * (mixture, bin) for a whole run.  2..4 sources: RESIDENT while the N x T slab fits 48 KiB of LDS
+ * (N T <= 3072), STREAMING above.  COMPOSED for 5 sources and more (measured slower in the kernel,
+ * profiles/fdica.txt), for IP2 and for more than 65535 mixtures.  -1 on a bad argument.  Host only. */
+int ssspy_fdica_route(int B, int N, int F, int T, int algorithm);
+
+/* n_steps >= 1 whole iterations of GradLaplaceFDICA / NaturalGradLaplaceFDICA / AuxLaplaceFDICA-IP1
+ * on W (B,F,N,N) in place, X (B,N,F,T), in one launch; the estimate, the weights and the
+ * covariances stay on chip.  loss_data and logdet (both or neither): step s leaves the contrast
+ * term sum_n mean_j 2 |y| of bin i of the state it STARTS from at
+ * loss_data[i * slot_stride + s * B + b] and log|det W_i| of that state in logdet likewise; entry
+ * n_steps is the final state (slot_stride >= (n_steps + 1) B; add over the bins in slot order with
+ * ssspy_fold_scalar_slots, F slots).  A singular bin bumps info[0].  fp64, no atomics on doubles,
+ * every sum in a fixed order.  2..8 sources (compiled per count; the slab in LDS when it fits 48 KiB,
+ * else re-read every step), SSSPY_ERR_UNSUPPORTED outside, for IP2 and above 65535 mixtures.
+ * replaces: ssspy/bss/fdica.py:629-650, :824-843, :1104-1116 and the loss at :216-223. */
+int ssspy_fdica_steps(const void *X, void *W, int B, int N, int F, int T, int algorithm,
+                      int holonomic, double step_size, int floor_kind, double floor_eps,
+                      int n_steps, double *loss_data, double *logdet, long long slot_stride,
+                      int *info, void *stream);
 
 /* ------------------------------------------------- FastIVA / FasterIVA, whitening, PCA */
 

@@ -47,6 +47,7 @@ def _units():
         ("iva_kernels.hip", "iva_kernels.o", []),
         ("grad_iva.hip", "grad_iva.o", []),
         ("fast_iva.hip", "fast_iva.o", []),
+        ("fdica.hip", "fdica.o", []),
         ("ipsdta.hip", "ipsdta.o", []),
         ("cacgmm.hip", "cacgmm.o", []),
         ("iss_fused.hip", "iss_fused.o", []),

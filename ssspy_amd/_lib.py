@@ -42,13 +42,16 @@ GMNMF_PLAN_FIELDS = ("packed", "trace_sources", "wide", "spatial_form", "basis_f
                      "loss_flags_offset")
 GMNMF_SPATIAL_LITERAL, GMNMF_SPATIAL_PACKED, GMNMF_SPATIAL_ROWS8 = range(3)
 GMNMF_BASIS_REGISTERS, GMNMF_BASIS_LDS_TILE, GMNMF_BASIS_MEMORY = range(3)
+# SSSPY_FDICA_*: `algorithm` of the FDICA entry points; SSSPY_FDICA_ROUTE_*: what ssspy_fdica_route returns
+FDICA_GRAD, FDICA_NATURAL_GRAD, FDICA_AUX_IP1, FDICA_AUX_IP2 = range(4)
+FDICA_ROUTE_RESIDENT, FDICA_ROUTE_STREAMING, FDICA_ROUTE_COMPOSED = range(3)
 MAX_PAIRS = 32
 # SSSPY_MAX_SOURCES (per-N kernels: IPA, both MNMF classes, the Hermitian operators; GaussMNMF's
 # channels and the ILRMA partition entry points stop there), SSSPY_RT_MAX_SOURCES (run-time-N kernels:
 # the shared operators, ILRMA, AuxIVA, FastGaussMNMF's channels and sources, GaussMNMF's sources),
 # SSSPY_MAX_BASIS
 MAX_SOURCES, RT_MAX_SOURCES, MAX_BASIS = 8, 16, 65536
-ABI_VERSION = 8  # SSSPY_ABI_VERSION of the include/ssspy_amd.h these prototypes mirror
+ABI_VERSION = 9  # SSSPY_ABI_VERSION of the include/ssspy_amd.h these prototypes mirror
 
 _p, _i, _d, _z = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_size_t
 _q = ctypes.c_longlong
@@ -135,6 +138,9 @@ PROTOTYPES = {
     "ssspy_iva_score_weight": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _d, _p]),
     "ssspy_iva_grad_step_logdet_slots": (_i, [_i, _i, _i]),
     "ssspy_iva_grad_step": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _d, _p, _p, _q, _p]),
+    "ssspy_fdica_weight": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _d, _p, _q, _p]),
+    "ssspy_fdica_route": (_i, [_i, _i, _i, _i, _i]),
+    "ssspy_fdica_steps": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _d, _i, _d, _i, _p, _p, _q, _p, _p]),
     "ssspy_fast_iva_weights": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _d, _p]),
     "ssspy_fast_iva_stats": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "ssspy_fast_iva_step": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p]),

@@ -722,6 +722,47 @@ def iva_grad_step(W, stats, natural, holonomic, step_size, info, logdet=None, lo
     return W
 
 
+# ------------------------------------------------------------------------------- FDICA
+def fdica_weight(Y, aux_form, flooring, weight=None, contrast=None, contrast_stride=0,
+                 want_weight=True):
+    """Laplace weights of the estimate Y (B, S, F, T): 1 / floor(|y|), or 2 / floor(2 |y|) with
+    ``aux_form``.  ``contrast``: the per-bin contrast term sum_s mean_j 2 |y| at
+    contrast[i * contrast_stride + b] (F slots, folded with ``fold_scalar_slots``)."""
+    B, S, F, T = Y.shape
+    if weight is None and want_weight:
+        weight = dv.empty((B, S, F, T), dv.f64, Y.device)
+    _lib.check(
+        _L().ssspy_fdica_weight(ptr(Y), ptr(weight), B, S, F, T, int(bool(aux_form)), flooring[0],
+                                flooring[1], ptr(contrast), int(contrast_stride), _st()),
+        "fdica_weight",
+    )
+    return weight
+
+
+def fdica_route(B, N, F, T, algorithm):
+    """The _lib.FDICA_ROUTE_* a shape takes.  Host only."""
+    route = int(_L().ssspy_fdica_route(B, N, F, T, int(algorithm)))
+    if route < 0:
+        raise ValueError("fdica_route: bad shape")
+    return route
+
+
+def fdica_steps(X, W, algorithm, holonomic, step_size, flooring, n_steps, info, loss_data=None,
+                logdet=None, slot_stride=0):
+    """``n_steps`` whole FDICA iterations on W (B, F, N, N) in place in one launch.  ``loss_data``
+    / ``logdet`` (F, slot_stride): the per-bin terms of the state every step starts from and, in
+    entry ``n_steps``, of the final state, at [i, s * B + b]."""
+    B, N, F, T = X.shape
+    assert tuple(W.shape) == (B, F, N, N)
+    _lib.check(
+        _L().ssspy_fdica_steps(ptr(X), ptr(W), B, N, F, T, int(algorithm), int(bool(holonomic)),
+                               float(step_size), flooring[0], flooring[1], int(n_steps),
+                               ptr(loss_data), ptr(logdet), int(slot_stride), ptr(info), _st()),
+        "fdica_steps",
+    )
+    return W
+
+
 # --------------------------------------------------------------- FastIVA / FasterIVA, whitening
 def fast_iva_weights(r2, d_contrast, dd_contrast, flooring, want_psi=True):
     """(phi, psi) (B, N, T) from the frame powers and the closures' values on the norms; psi None

@@ -23,6 +23,10 @@ _DEFAULTS = {
     # FastGaussMNMF keeps |Q x|^2 between the spatial and the NMF passes; False: every pass
     # recomputes it (what shapes without a hand-over buffer run)
     "handover": True,
+    # FDICA runs whole iterations of a (mixture, bin) inside ssspy_fdica_steps where
+    # ssspy_fdica_route allows; False: the per-iteration operators (what IP2, user closures, host
+    # floors and 9..16 sources run)
+    "fdica_kernel": True,
 }
 VALUES = dict(_DEFAULTS)  # (tests: monkeypatch.setitem(_routes.VALUES, "implied_filter", False))
 
