@@ -98,8 +98,9 @@ const char *ssspy_amd_version(void);
  * 6: ssspy_gmnmf_route added (additive).
  * 7: the FastIVA / FasterIVA entry points and ssspy_whitening_filter added (additive).
  * 8: the IPSDTA entry points and ssspy_matmul3 added (additive).
- * 9: the FDICA entry points added (additive). */
-#define SSSPY_ABI_VERSION 9
+ * 9: the FDICA entry points added (additive).
+ * 10: ssspy_prox_neg_logdet and the PDSBSS entry points added (additive). */
+#define SSSPY_ABI_VERSION 10
 int ssspy_abi_version(void);
 const char *ssspy_last_error(void);
 
@@ -672,6 +673,65 @@ int ssspy_fdica_steps(const void *X, void *W, int B, int N, int F, int T, int al
                       int holonomic, double step_size, int floor_kind, double floor_eps,
                       int n_steps, double *loss_data, double *logdet, long long slot_stride,
                       int *info, void *stream);
+
+/* ------------------------------------------------- PDSBSS (primal-dual splitting), prox of -log|det| */
+
+/* prox_{-step_size log|det|}(X) = U diag(f(sigma)) V^H, f(s) = (s + sqrt(s^2 + 4 step_size)) / 2, for n
+ * complex N x N matrices X = U diag(sigma) V^H; out (n,N,N) may be X.  One-sided (Hestenes) complex
+ * Jacobi on X itself (error eps * kappa, not the eps * kappa^2 of an eigen-decomposition of X X^H),
+ * a lane per matrix.  The result does not depend on phases, order or the basis inside a repeated
+ * singular value; where a singular value is exactly zero it is not determined, and the kernel
+ * returns finite numbers whose singular values are f(sigma).  N in [1, SSSPY_RT_MAX_SOURCES]: 1..8
+ * compiled per size, 9..16 with the size at run time; SSSPY_ERR_UNSUPPORTED outside.
+ * replaces: ssspy/linalg/prox.py:62-91. */
+int ssspy_prox_neg_logdet(const void *X, void *out, long long n, int N, double step_size,
+                          void *stream);
+
+/* `kind` of ssspy_pdsbss_dual_step: how Yt = Z - prox(Z, step_size) is formed from
+ * Z = dual_q + W2 x (ref: ssspy/linalg/prox.py:6-33, ssspy/bss/pdsbss.py:211-214, :408-409) */
+enum {
+  SSSPY_PROX_L1 = 0,          /* l1: the shrinkage per element                                     */
+  SSSPY_PROX_L21_SOURCES = 1, /* l21, the group norm over sources (axis2 = 0): inside a lane       */
+  SSSPY_PROX_L21_BINS = 2,    /* l21 over bins (axis2 = 1, the IVA penalty): r2 of ..._bin_norms   */
+  SSSPY_PROX_L21_FRAMES = 3,  /* l21 over frames (axis2 = 2): inside the workgroup of a bin        */
+  SSSPY_PROX_MASK = 4,        /* Yt = Z - aux Z, aux (B,N,F,T) complex128: a mask from the host    */
+  SSSPY_PROX_GIVEN = 5,       /* Yt = aux (B,N,F,T) complex128, formed on the host                 */
+};
+
+/* The PDSBSS entry points: X (B,N,F,T), W and W2 (B,F,N,N), the dual variable (B,Q,N,F,T) with Q
+ * penalties, all complex128; N in [1, 16], B <= 65535, SSSPY_ERR_UNSUPPORTED outside.  A penalty's
+ * slice of the dual variable is passed as dual_q = dual + q N F T with dual_batch_stride = Q N F T
+ * elements between mixtures.  No atomics, every sum in a fixed order. */
+
+/* XY[b,i] = (sum_q dual[b,q])_i X[b]_i^H, (B,F,N,N): the contraction over penalties and frames.
+ * replaces: ssspy/bss/pdsbss.py:205-206, :404. */
+int ssspy_pdsbss_contract(const void *dual, const void *X, void *XY, int B, int Q, int N, int F,
+                          int T, void *stream);
+
+/* Per bin Wt = prox_{-mu1 log|det|}(W - mu1 mu2 XY), W2 = 2 Wt - W (the filter the dual step reads) and
+ * W <- relaxation Wt + (1 - relaxation) W in place.
+ * replaces: ssspy/bss/pdsbss.py:207-208, :218. */
+int ssspy_pdsbss_filter_step(void *W, const void *XY, void *W2, int B, int F, int N, double mu1,
+                             double mu2, double relaxation, void *stream);
+
+/* r2[b,n,j] = sum_i |Z[b,n,i,j]|^2 (B,N,T) f64 with Z = dual_q + W2 x: partial sums over chunks of
+ * bins in the workspace, added in chunk order. */
+size_t ssspy_pdsbss_bin_norms_workspace_bytes(int B, int N, int F, int T);
+int ssspy_pdsbss_bin_norms(const void *X, const void *W2, const void *dual_q,
+                           long long dual_batch_stride, double *r2, int B, int N, int F, int T,
+                           void *workspace, size_t workspace_bytes, void *stream);
+
+/* dual_q <- relaxation Yt + (1 - relaxation) dual_q with Yt by `kind` (SSSPY_PROX_L1 .. _GIVEN);
+ * r2: SSSPY_PROX_L21_BINS only; aux: SSSPY_PROX_MASK / _GIVEN only (else NULL).
+ * replaces: ssspy/bss/pdsbss.py:211-214, :219, :408-412. */
+int ssspy_pdsbss_dual_step(const void *X, const void *W2, void *dual_q, long long dual_batch_stride,
+                           int kind, double step_size, double relaxation, const double *r2,
+                           const void *aux, int B, int N, int F, int T, void *stream);
+
+/* Z = dual_q + W2 x into Z (B,N,F,T), for proximal operators and masks that run on the host. */
+int ssspy_pdsbss_form_z(const void *X, const void *W2, const void *dual_q,
+                        long long dual_batch_stride, void *Z, int B, int N, int F, int T,
+                        void *stream);
 
 /* ------------------------------------------------- FastIVA / FasterIVA, whitening, PCA */
 

@@ -48,6 +48,7 @@ def _units():
         ("grad_iva.hip", "grad_iva.o", []),
         ("fast_iva.hip", "fast_iva.o", []),
         ("fdica.hip", "fdica.o", []),
+        ("pdsbss.hip", "pdsbss.o", []),
         ("ipsdta.hip", "ipsdta.o", []),
         ("cacgmm.hip", "cacgmm.o", []),
         ("iss_fused.hip", "iss_fused.o", []),

@@ -763,6 +763,77 @@ def fdica_steps(X, W, algorithm, holonomic, step_size, flooring, n_steps, info, 
     return W
 
 
+# ------------------------------------------------------------------------------ PDSBSS
+def prox_neg_logdet(X, step_size, out=None):
+    """prox of -step_size log|det| of the matrices X (..., N, N), a device tensor."""
+    N = X.shape[-1]
+    if out is None:
+        out = dv.empty(tuple(X.shape), dv.c128, X.device)
+    _lib.check(_L().ssspy_prox_neg_logdet(ptr(X), ptr(out), X.numel() // (N * N), N,
+                                          float(step_size), _st()), "prox_neg_logdet")
+    return out
+
+
+def pdsbss_contract(dual, X, out=None):
+    """XY (B, F, N, N) = (sum_q dual_q) X^H per bin; dual (B, Q, N, F, T)."""
+    B, Q, N, F, T = dual.shape
+    assert tuple(X.shape) == (B, N, F, T)
+    if out is None:
+        out = dv.empty((B, F, N, N), dv.c128, X.device)
+    _lib.check(_L().ssspy_pdsbss_contract(ptr(dual), ptr(X), ptr(out), B, Q, N, F, T, _st()),
+               "pdsbss_contract")
+    return out
+
+
+def pdsbss_filter_step(W, XY, W2, mu1, mu2, relaxation):
+    """Wt = prox(W - mu1 mu2 XY, mu1), W2 = 2 Wt - W, W <- relaxed, in place; all (B, F, N, N)."""
+    B, F, N, _ = W.shape
+    assert tuple(XY.shape) == tuple(W2.shape) == (B, F, N, N)
+    _lib.check(_L().ssspy_pdsbss_filter_step(ptr(W), ptr(XY), ptr(W2), B, F, N, float(mu1),
+                                             float(mu2), float(relaxation), _st()),
+               "pdsbss_filter_step")
+    return W
+
+
+def _dual_slice(dual, q):
+    """(pointer to penalty q of the dual variable, elements between mixtures, (B, N, F, T))."""
+    B, Q, N, F, T = dual.shape
+    assert dual.is_contiguous()
+    return dual.data_ptr() + 16 * q * N * F * T, Q * N * F * T, (B, N, F, T)
+
+
+def pdsbss_bin_norms(X, W2, dual, q, out=None):
+    """r2 (B, N, T): sum over bins of |dual_q + W2 x|^2."""
+    dq, stride, (B, N, F, T) = _dual_slice(dual, q)
+    if out is None:
+        out = dv.empty((B, N, T), dv.f64, X.device)
+    ws, ws_bytes = _scratch(_L().ssspy_pdsbss_bin_norms_workspace_bytes(B, N, F, T), X.device)
+    _lib.check(_L().ssspy_pdsbss_bin_norms(ptr(X), ptr(W2), dq, stride, ptr(out), B, N, F, T,
+                                           ptr(ws), ws_bytes, _st()), "pdsbss_bin_norms")
+    return out
+
+
+def pdsbss_dual_step(X, W2, dual, q, kind, step_size, relaxation, r2=None, aux=None):
+    """dual_q <- relaxation (Z - prox(Z)) + (1 - relaxation) dual_q in place, by _lib.PROX_*."""
+    dq, stride, (B, N, F, T) = _dual_slice(dual, q)
+    assert aux is None or tuple(aux.shape) == (B, N, F, T)
+    assert r2 is None or tuple(r2.shape) == (B, N, T)
+    _lib.check(_L().ssspy_pdsbss_dual_step(ptr(X), ptr(W2), dq, stride, int(kind), float(step_size),
+                                           float(relaxation), ptr(r2), ptr(aux), B, N, F, T, _st()),
+               "pdsbss_dual_step")
+    return dual
+
+
+def pdsbss_form_z(X, W2, dual, q, out=None):
+    """Z = dual_q + W2 x, (B, N, F, T)."""
+    dq, stride, (B, N, F, T) = _dual_slice(dual, q)
+    if out is None:
+        out = dv.empty((B, N, F, T), dv.c128, X.device)
+    _lib.check(_L().ssspy_pdsbss_form_z(ptr(X), ptr(W2), dq, stride, ptr(out), B, N, F, T, _st()),
+               "pdsbss_form_z")
+    return out
+
+
 # --------------------------------------------------------------- FastIVA / FasterIVA, whitening
 def fast_iva_weights(r2, d_contrast, dd_contrast, flooring, want_psi=True):
     """(phi, psi) (B, N, T) from the frame powers and the closures' values on the norms; psi None

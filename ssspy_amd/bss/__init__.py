@@ -1,4 +1,4 @@
-from . import base, cacgmm, fdica, ilrma, ipsdta, iva, mnmf
+from . import base, cacgmm, fdica, ilrma, ipsdta, iva, mnmf, pdsbss, proxbss
 from .base import IterativeMethodBase
 from .cacgmm import CACGMM, CACGMMBase
 from .fdica import (
@@ -12,8 +12,11 @@ from .fdica import (
     NaturalGradLaplaceFDICA,
 )
 from .ipsdta import TIPSDTA, BlockDecompositionIPSDTABase, GaussIPSDTA, IPSDTABase
+from .pdsbss import PDSBSS, MaskingPDSBSS, PDSBSSBase
+from .proxbss import ProxBSSBase
 
 __all__ = ["IterativeMethodBase", "CACGMM", "CACGMMBase", "IPSDTABase", "BlockDecompositionIPSDTABase",
            "GaussIPSDTA", "TIPSDTA", "FDICABase", "GradFDICABase", "GradFDICA", "NaturalGradFDICA",
-           "AuxFDICA", "GradLaplaceFDICA", "NaturalGradLaplaceFDICA", "AuxLaplaceFDICA", "base",
-           "cacgmm", "fdica", "ilrma", "ipsdta", "iva", "mnmf"]
+           "AuxFDICA", "GradLaplaceFDICA", "NaturalGradLaplaceFDICA", "AuxLaplaceFDICA",
+           "ProxBSSBase", "PDSBSSBase", "PDSBSS", "MaskingPDSBSS", "base", "cacgmm", "fdica", "ilrma",
+           "ipsdta", "iva", "mnmf", "pdsbss", "proxbss"]

@@ -15,8 +15,9 @@ import numpy as np
 from .. import _device as dv
 from .. import _lib
 from .._device import ptr
+from . import prox  # noqa: F401
 
-__all__ = ["solve", "inv2", "eigh", "eigh2", "sqrtmh", "invsqrtmh", "gmeanmh", "lqpqm2"]
+__all__ = ["solve", "inv2", "eigh", "eigh2", "sqrtmh", "invsqrtmh", "gmeanmh", "lqpqm2", "prox"]
 
 
 def _flat(a, tail):
