@@ -99,8 +99,9 @@ const char *ssspy_amd_version(void);
  * 7: the FastIVA / FasterIVA entry points and ssspy_whitening_filter added (additive).
  * 8: the IPSDTA entry points and ssspy_matmul3 added (additive).
  * 9: the FDICA entry points added (additive).
- * 10: ssspy_prox_neg_logdet and the PDSBSS entry points added (additive). */
-#define SSSPY_ABI_VERSION 10
+ * 10: ssspy_prox_neg_logdet and the PDSBSS entry points added (additive).
+ * 11: the HVA entry points added (additive). */
+#define SSSPY_ABI_VERSION 11
 int ssspy_abi_version(void);
 const char *ssspy_last_error(void);
 
@@ -732,6 +733,49 @@ int ssspy_pdsbss_dual_step(const void *X, const void *W2, void *dual_q, long lon
 int ssspy_pdsbss_form_z(const void *X, const void *W2, const void *dual_q,
                         long long dual_batch_stride, void *Z, int B, int N, int F, int T,
                         void *stream);
+
+/* ------------------------------------------------- HVA (harmonic vector analysis): the mask of
+ * MaskingPDSHVA inside the dual step of MaskingPDSBSS */
+
+/* `route` of the HVA entry points: which transform the cepstral pass runs along the bins */
+enum {
+  SSSPY_HVA_ROUTE_AUTO = 0,   /* FFT where it exists, else DIRECT                                   */
+  SSSPY_HVA_ROUTE_FFT = 1,    /* F - 1 a power of two, F <= 4097: a radix-2 FFT of length 2 (F - 1)
+                                 resident in LDS, two frames per complex transform                  */
+  SSSPY_HVA_ROUTE_DIRECT = 2, /* any 2 <= F <= 8192: the O(F^2) sum from the cosine table           */
+};
+
+/* The route `route` (SSSPY_HVA_ROUTE_*) resolves to for F bins: _FFT or _DIRECT; -1 where the
+ * request cannot be served (F < 2, F > 8192, _FFT for an F it does not exist for).  Host only. */
+int ssspy_hva_route(int F, int route);
+
+/* table[j] = cos(pi j / (F - 1)), j < 2 (F - 1), f64: the argument is reduced to [0, pi / 2] in
+ * integers first.  Both routes read it (the direct sum at (j k) mod 2 (F - 1), the FFT as twiddles). */
+int ssspy_hva_cos_table(double *table, int F, void *stream);
+
+/* The cepstral pass: per (mixture, source, frame) column of Z = dual_q + W2 x, along the bins
+ *   a = floor(|Z|), zeta = log a, m = mean_f zeta, rho = zeta - m,
+ *   nu = D(rho) / (2 (F - 1)), sigma = min(1, nu), mask_iter times sigma <- (1 - cos(pi sigma)) / 2,
+ *   varrho = D(sigma nu) + m,
+ * D(c)_k = c_0 + (-1)^k c_{F-1} + 2 sum_{0<j<F-1} c_j cos(pi j k / (F - 1)) (the DCT-I: both irfft
+ * calls of the reference on a real length-F input).  varrho (B,N,F,T) f64.  A column whose mean is not
+ * finite (log 0 without a floor) comes out as NaN, as from the reference.  A workgroup holds the
+ * F x (tile of frames) slab of one source in LDS; no atomics, every sum in a fixed order.
+ * N in [1, 16], B <= 65535, F and route as ssspy_hva_route allows; SSSPY_ERR_UNSUPPORTED outside.
+ * replaces: ssspy/bss/hva.py:91-111. */
+int ssspy_hva_cepstrum(const void *X, const void *W2, const void *dual_q,
+                       long long dual_batch_stride, const double *table, double *varrho, int B,
+                       int N, int F, int T, int floor_kind, double floor_eps, int mask_iter,
+                       int route, void *stream);
+
+/* The masked dual step: per (b, f, t) Z again, mask_n = exp(2 g (varrho_n - max)) /
+ * (sum_n' exp(2 (varrho_n' - max)))^g with g = attenuation (the reference's (v / sum v)^g,
+ * v = exp(2 varrho), wherever its exp neither overflows nor underflows to 0 / 0), Yt = Z - mask Z and
+ * dual_q <- relaxation Yt + (1 - relaxation) dual_q in place.
+ * replaces: ssspy/bss/hva.py:112-115 with ssspy/bss/pdsbss.py:408-412. */
+int ssspy_hva_dual_step(const void *X, const void *W2, void *dual_q, long long dual_batch_stride,
+                        const double *varrho, double attenuation, double relaxation, int B, int N,
+                        int F, int T, void *stream);
 
 /* ------------------------------------------------- FastIVA / FasterIVA, whitening, PCA */
 

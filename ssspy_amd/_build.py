@@ -49,6 +49,7 @@ def _units():
         ("fast_iva.hip", "fast_iva.o", []),
         ("fdica.hip", "fdica.o", []),
         ("pdsbss.hip", "pdsbss.o", []),
+        ("hva.hip", "hva.o", []),
         ("ipsdta.hip", "ipsdta.o", []),
         ("cacgmm.hip", "cacgmm.o", []),
         ("iss_fused.hip", "iss_fused.o", []),

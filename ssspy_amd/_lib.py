@@ -47,13 +47,15 @@ FDICA_GRAD, FDICA_NATURAL_GRAD, FDICA_AUX_IP1, FDICA_AUX_IP2 = range(4)
 FDICA_ROUTE_RESIDENT, FDICA_ROUTE_STREAMING, FDICA_ROUTE_COMPOSED = range(3)
 # SSSPY_PROX_*: `kind` of ssspy_pdsbss_dual_step
 PROX_L1, PROX_L21_SOURCES, PROX_L21_BINS, PROX_L21_FRAMES, PROX_MASK, PROX_GIVEN = range(6)
+# SSSPY_HVA_ROUTE_*: `route` of the HVA entry points and what ssspy_hva_route returns
+HVA_ROUTE_AUTO, HVA_ROUTE_FFT, HVA_ROUTE_DIRECT = range(3)
 MAX_PAIRS = 32
 # SSSPY_MAX_SOURCES (per-N kernels: IPA, both MNMF classes, the Hermitian operators; GaussMNMF's
 # channels and the ILRMA partition entry points stop there), SSSPY_RT_MAX_SOURCES (run-time-N kernels:
 # the shared operators, ILRMA, AuxIVA, FastGaussMNMF's channels and sources, GaussMNMF's sources),
 # SSSPY_MAX_BASIS
 MAX_SOURCES, RT_MAX_SOURCES, MAX_BASIS = 8, 16, 65536
-ABI_VERSION = 10  # SSSPY_ABI_VERSION of the include/ssspy_amd.h these prototypes mirror
+ABI_VERSION = 11  # SSSPY_ABI_VERSION of the include/ssspy_amd.h these prototypes mirror
 
 _p, _i, _d, _z = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_size_t
 _q = ctypes.c_longlong
@@ -150,6 +152,10 @@ PROTOTYPES = {
     "ssspy_pdsbss_bin_norms": (_i, [_p, _p, _p, _q, _p, _i, _i, _i, _i, _p, _z, _p]),
     "ssspy_pdsbss_dual_step": (_i, [_p, _p, _p, _q, _i, _d, _d, _p, _p, _i, _i, _i, _i, _p]),
     "ssspy_pdsbss_form_z": (_i, [_p, _p, _p, _q, _p, _i, _i, _i, _i, _p]),
+    "ssspy_hva_route": (_i, [_i, _i]),
+    "ssspy_hva_cos_table": (_i, [_p, _i, _p]),
+    "ssspy_hva_cepstrum": (_i, [_p, _p, _p, _q, _p, _p, _i, _i, _i, _i, _i, _d, _i, _i, _p]),
+    "ssspy_hva_dual_step": (_i, [_p, _p, _p, _q, _p, _d, _d, _i, _i, _i, _i, _p]),
     "ssspy_fast_iva_weights": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _d, _p]),
     "ssspy_fast_iva_stats": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "ssspy_fast_iva_step": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p]),

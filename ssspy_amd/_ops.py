@@ -834,6 +834,47 @@ def pdsbss_form_z(X, W2, dual, q, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------ HVA
+def hva_route(F, route=_lib.HVA_ROUTE_AUTO):
+    """The transform route (_lib.HVA_ROUTE_FFT / _DIRECT) the cepstral pass takes for F bins when
+    asked for ``route``.  Host only."""
+    got = int(_L().ssspy_hva_route(int(F), int(route)))
+    if got < 0:
+        raise ValueError("hva_route: no such route for {} bins".format(F))
+    return got
+
+
+def hva_cos_table(F, dev):
+    """cos(pi j / (F - 1)), j < 2 (F - 1): the table both transform routes read."""
+    table = dv.empty((2 * (F - 1),), dv.f64, dev)
+    _lib.check(_L().ssspy_hva_cos_table(ptr(table), int(F), _st()), "hva_cos_table")
+    return table
+
+
+def hva_cepstrum(X, W2, dual, q, table, flooring, mask_iter, route=_lib.HVA_ROUTE_AUTO, out=None):
+    """varrho (B, N, F, T) f64 of Z = dual_q + W2 x: the log-magnitude after the cosine shrinkage
+    of its cepstrum along the bins (see the header)."""
+    dq, stride, (B, N, F, T) = _dual_slice(dual, q)
+    assert tuple(table.shape) == (2 * (F - 1),)
+    if out is None:
+        out = dv.empty((B, N, F, T), dv.f64, X.device)
+    assert tuple(out.shape) == (B, N, F, T)
+    _lib.check(_L().ssspy_hva_cepstrum(ptr(X), ptr(W2), dq, stride, ptr(table), ptr(out), B, N, F, T,
+                                       flooring[0], float(flooring[1]), int(mask_iter), int(route),
+                                       _st()), "hva_cepstrum")
+    return out
+
+
+def hva_dual_step(X, W2, dual, q, varrho, attenuation, relaxation):
+    """dual_q <- relaxation (Z - mask Z) + (1 - relaxation) dual_q in place, the mask the softmax of
+    2 varrho over sources to the power ``attenuation``."""
+    dq, stride, (B, N, F, T) = _dual_slice(dual, q)
+    assert tuple(varrho.shape) == (B, N, F, T)
+    _lib.check(_L().ssspy_hva_dual_step(ptr(X), ptr(W2), dq, stride, ptr(varrho), float(attenuation),
+                                        float(relaxation), B, N, F, T, _st()), "hva_dual_step")
+    return dual
+
+
 # --------------------------------------------------------------- FastIVA / FasterIVA, whitening
 def fast_iva_weights(r2, d_contrast, dd_contrast, flooring, want_psi=True):
     """(phi, psi) (B, N, T) from the frame powers and the closures' values on the norms; psi None

@@ -1,4 +1,4 @@
-from . import base, cacgmm, fdica, ilrma, ipsdta, iva, mnmf, pdsbss, proxbss
+from . import base, cacgmm, fdica, hva, ilrma, ipsdta, iva, mnmf, pdsbss, proxbss
 from .base import IterativeMethodBase
 from .cacgmm import CACGMM, CACGMMBase
 from .fdica import (
@@ -11,6 +11,7 @@ from .fdica import (
     NaturalGradFDICA,
     NaturalGradLaplaceFDICA,
 )
+from .hva import HVA, MaskingPDSHVA
 from .ipsdta import TIPSDTA, BlockDecompositionIPSDTABase, GaussIPSDTA, IPSDTABase
 from .pdsbss import PDSBSS, MaskingPDSBSS, PDSBSSBase
 from .proxbss import ProxBSSBase
@@ -18,5 +19,5 @@ from .proxbss import ProxBSSBase
 __all__ = ["IterativeMethodBase", "CACGMM", "CACGMMBase", "IPSDTABase", "BlockDecompositionIPSDTABase",
            "GaussIPSDTA", "TIPSDTA", "FDICABase", "GradFDICABase", "GradFDICA", "NaturalGradFDICA",
            "AuxFDICA", "GradLaplaceFDICA", "NaturalGradLaplaceFDICA", "AuxLaplaceFDICA",
-           "ProxBSSBase", "PDSBSSBase", "PDSBSS", "MaskingPDSBSS", "base", "cacgmm", "fdica", "ilrma",
-           "ipsdta", "iva", "mnmf", "pdsbss", "proxbss"]
+           "ProxBSSBase", "PDSBSSBase", "PDSBSS", "MaskingPDSBSS", "MaskingPDSHVA", "HVA", "base", "cacgmm",
+           "fdica", "hva", "ilrma", "ipsdta", "iva", "mnmf", "pdsbss", "proxbss"]

@@ -11,6 +11,7 @@
 // k_pds_bin_norms (over bins: partial sums per chunk of bins, added in chunk order).
 // fp64 / complex128, no atomics, every sum in a fixed order: two runs give the same bits.
 #include "common.hpp"
+#include "pds_common.hpp"
 #include "prox_svd.hpp"
 
 namespace ssspy {
@@ -18,7 +19,6 @@ namespace ssspy {
 namespace {
 
 constexpr int RM = SSSPY_RT_MAX_SOURCES;
-constexpr int PDS_THREADS = 256;
 constexpr int PDS_MAX_CHUNKS = FOLD_GROUP;  // (one level of k_fold_slabs: no scratch)
 // a `kind` of k_pds_dual_step past the public SSSPY_PROX_* ones: Z to zout, the dual untouched
 // (ssspy_pdsbss_form_z; ssspy_pdsbss_dual_step refuses it)
@@ -150,26 +150,6 @@ __global__ __launch_bounds__(PDS_THREADS) void k_pds_contract(const c128 *__rest
   }
 }
 
-// z_n = d_n + sum_m W2[n][m] x_m for the N rows of one (bin, frame); Wn: row-major N x N
-template <int G, typename WPtr>
-__device__ __forceinline__ void pds_form_z(c128 (&z)[G], const c128 *__restrict__ Xb,
-                                           const c128 *Db, WPtr Wn, int N, long long FT, int j) {
-  c128 x[G];
-#pragma unroll
-  for (int m = 0; m < G; ++m) x[m] = m < N ? Xb[m * FT + j] : cmake(0.0, 0.0);
-#pragma unroll
-  for (int n = 0; n < G; ++n) {
-    z[n] = cmake(0.0, 0.0);
-    if (n < N) {
-      c128 y = cmake(0.0, 0.0);
-#pragma unroll
-      for (int m = 0; m < G; ++m)
-        if (m < N) cfma(y, Wn[n * N + m], x[m]);
-      z[n] = cadd(Db[n * FT + j], y);
-    }
-  }
-}
-
 // ---- the group norms of l21 over bins: part[c,b,n,j] = sum over the bins of chunk c of |Z|^2, in
 // bin order.  grid (ceil(T / 256), C, B); a thread owns one frame.  No barriers.
 template <int G>
@@ -288,20 +268,6 @@ __global__ __launch_bounds__(PDS_THREADS) void k_pds_dual_step(
       }
     }
   }
-}
-
-static int pow2_group(int N) { return N <= 2 ? 2 : (N <= 4 ? 4 : (N <= 8 ? 8 : 16)); }
-
-#define SSSPY_PDS_DISPATCH_G(N_, CALL)               \
-  switch (pow2_group(N_)) {                          \
-    case 2: { constexpr int GG = 2; CALL; } break;   \
-    case 4: { constexpr int GG = 4; CALL; } break;   \
-    case 8: { constexpr int GG = 8; CALL; } break;   \
-    default: { constexpr int GG = 16; CALL; } break; \
-  }
-
-static bool pds_shape_ok(int B, int N, int F, int T) {
-  return B > 0 && B <= 65535 && N >= 1 && N <= RM && F > 0 && T > 0;
 }
 
 // bins per chunk and chunks of the l21-over-bins norm pass
