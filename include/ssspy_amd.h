@@ -734,6 +734,55 @@ int ssspy_pdsbss_form_z(const void *X, const void *W2, const void *dual_q,
                         long long dual_batch_stride, void *Z, int B, int N, int F, int T,
                         void *stream);
 
+/* ------------------------------------------------- ADMMBSS / MaskingADMMBSS
+ * (additive to ABI version 11: no existing argument list changed)
+ *
+ * X (B,N,F,T), W, Ainv, R, auxiliary1 and dual1 (B,F,N,N), auxiliary2 and dual2 (B,Q,N,F,T) with Q
+ * penalties, all complex128; N in [1, 16], B <= 65535, SSSPY_ERR_UNSUPPORTED outside.  A penalty's
+ * slices are passed as aux2_q = auxiliary2 + q N F T and dual2_q = dual2 + q N F T with batch_stride =
+ * Q N F T elements between mixtures.  `kind` is SSSPY_PROX_*.  No atomics, every sum in a fixed
+ * order. */
+
+/* Once per call: Ainv[b,i] = (Q conj(X_i) X_i^T + I)^-1, Hermitian positive definite, by a Cholesky
+ * factorisation per bin (the Gram matrix in the order of ssspy_admmbss_contract).
+ * replaces: ssspy/bss/admmbss.py:230-231, :236 (the left-hand side), :424-425, :430. */
+int ssspy_admmbss_gram_inverse(const void *X, void *Ainv, int B, int Q, int N, int F, int T,
+                               void *stream);
+
+/* R[b,i] = (sum_q (auxiliary2[b,q] - dual2[b,q]))_i X[b]_i^H, (B,F,N,N).
+ * replaces: ssspy/bss/admmbss.py:233-234, :427-428 (transposed as :236 / :430 read it). */
+int ssspy_admmbss_contract(const void *aux2, const void *dual2, const void *X, void *R, int B, int Q,
+                           int N, int F, int T, void *stream);
+
+/* Per bin W = Ainv (auxiliary1 - dual1 + R), U = relaxation W + (1 - relaxation) auxiliary1,
+ * auxiliary1 <- prox_{-log|det| / rho}(U + dual1), dual1 <- dual1 + U - auxiliary1; W is written,
+ * aux1 and dual1 in place.  An argument U + dual1 that is exactly zero gives sqrt(1 / rho) I (what the
+ * reference returns there: LAPACK's U = V = I).
+ * replaces: ssspy/bss/admmbss.py:232, :236, :239, :242, :252, :426, :430, :433, :435, :437. */
+int ssspy_admmbss_filter_step(const void *Ainv, const void *R, void *W, void *aux1, void *dual1, int B,
+                              int F, int N, double rho, double relaxation, void *stream);
+
+/* r2[b,n,j] = sum_i |Z[b,n,i,j]|^2 (B,N,T) f64 with Z = relaxation W x + (1 - relaxation) aux2_q +
+ * dual2_q: partial sums over chunks of bins in the workspace, added in chunk order. */
+size_t ssspy_admmbss_bin_norms_workspace_bytes(int B, int N, int F, int T);
+int ssspy_admmbss_bin_norms(const void *X, const void *W, const void *aux2_q, const void *dual2_q,
+                            long long batch_stride, double relaxation, double *r2, int B, int N, int F,
+                            int T, void *workspace, size_t workspace_bytes, void *stream);
+
+/* aux2_q <- prox(Z, step_size) by `kind` (SSSPY_PROX_L1 .. _GIVEN) and dual2_q <- Z - aux2_q in place;
+ * Z as above, formed in registers (aux2_q is not read when relaxation == 1).  r2: SSSPY_PROX_L21_BINS
+ * only; given (B,N,F,T): SSSPY_PROX_MASK (the mask: aux2_q <- given Z) / _GIVEN (prox(Z) itself).
+ * replaces: ssspy/bss/admmbss.py:237, :240, :246-250, :253, :431, :434, :436, :438. */
+int ssspy_admmbss_aux_step(const void *X, const void *W, void *aux2_q, void *dual2_q,
+                           long long batch_stride, int kind, double step_size, double relaxation,
+                           const double *r2, const void *given, int B, int N, int F, int T,
+                           void *stream);
+
+/* Z into Z (B,N,F,T), for proximal operators and masks that run on the host. */
+int ssspy_admmbss_form_z(const void *X, const void *W, const void *aux2_q, const void *dual2_q,
+                         long long batch_stride, double relaxation, void *Z, int B, int N, int F,
+                         int T, void *stream);
+
 /* ------------------------------------------------- HVA (harmonic vector analysis): the mask of
  * MaskingPDSHVA inside the dual step of MaskingPDSBSS */
 

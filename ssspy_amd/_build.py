@@ -50,6 +50,7 @@ def _units():
         ("fdica.hip", "fdica.o", []),
         ("pdsbss.hip", "pdsbss.o", []),
         ("hva.hip", "hva.o", []),
+        ("admmbss.hip", "admmbss.o", []),
         ("ipsdta.hip", "ipsdta.o", []),
         ("cacgmm.hip", "cacgmm.o", []),
         ("iss_fused.hip", "iss_fused.o", []),

@@ -152,6 +152,13 @@ PROTOTYPES = {
     "ssspy_pdsbss_bin_norms": (_i, [_p, _p, _p, _q, _p, _i, _i, _i, _i, _p, _z, _p]),
     "ssspy_pdsbss_dual_step": (_i, [_p, _p, _p, _q, _i, _d, _d, _p, _p, _i, _i, _i, _i, _p]),
     "ssspy_pdsbss_form_z": (_i, [_p, _p, _p, _q, _p, _i, _i, _i, _i, _p]),
+    "ssspy_admmbss_gram_inverse": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
+    "ssspy_admmbss_contract": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "ssspy_admmbss_filter_step": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _d, _d, _p]),
+    "ssspy_admmbss_bin_norms_workspace_bytes": (_z, [_i, _i, _i, _i]),
+    "ssspy_admmbss_bin_norms": (_i, [_p, _p, _p, _p, _q, _d, _p, _i, _i, _i, _i, _p, _z, _p]),
+    "ssspy_admmbss_aux_step": (_i, [_p, _p, _p, _p, _q, _i, _d, _d, _p, _p, _i, _i, _i, _i, _p]),
+    "ssspy_admmbss_form_z": (_i, [_p, _p, _p, _p, _q, _d, _p, _i, _i, _i, _i, _p]),
     "ssspy_hva_route": (_i, [_i, _i]),
     "ssspy_hva_cos_table": (_i, [_p, _i, _p]),
     "ssspy_hva_cepstrum": (_i, [_p, _p, _p, _q, _p, _p, _i, _i, _i, _i, _i, _d, _i, _i, _p]),

@@ -834,6 +834,81 @@ def pdsbss_form_z(X, W2, dual, q, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------ ADMMBSS
+def admmbss_gram_inverse(X, Q, out=None):
+    """Ainv (B, F, N, N) = (Q conj(X) X^T + I)^-1 per bin."""
+    B, N, F, T = X.shape
+    if out is None:
+        out = dv.empty((B, F, N, N), dv.c128, X.device)
+    _lib.check(_L().ssspy_admmbss_gram_inverse(ptr(X), ptr(out), B, int(Q), N, F, T, _st()),
+               "admmbss_gram_inverse")
+    return out
+
+
+def admmbss_contract(aux2, dual2, X, out=None):
+    """R (B, F, N, N) = (sum_q (aux2_q - dual2_q)) X^H per bin; aux2, dual2 (B, Q, N, F, T)."""
+    B, Q, N, F, T = aux2.shape
+    assert tuple(dual2.shape) == (B, Q, N, F, T) and tuple(X.shape) == (B, N, F, T)
+    assert aux2.is_contiguous() and dual2.is_contiguous()
+    if out is None:
+        out = dv.empty((B, F, N, N), dv.c128, X.device)
+    _lib.check(_L().ssspy_admmbss_contract(ptr(aux2), ptr(dual2), ptr(X), ptr(out), B, Q, N, F, T,
+                                           _st()), "admmbss_contract")
+    return out
+
+
+def admmbss_filter_step(Ainv, R, W, aux1, dual1, rho, relaxation):
+    """W = Ainv (aux1 - dual1 + R), U = relaxation W + (1 - relaxation) aux1,
+    aux1 <- prox.neg_logdet(U + dual1, 1 / rho), dual1 <- dual1 + U - aux1; all (B, F, N, N)."""
+    B, F, N, _ = W.shape
+    for t in (Ainv, R, aux1, dual1):
+        assert tuple(t.shape) == (B, F, N, N) and t.is_contiguous()
+    _lib.check(_L().ssspy_admmbss_filter_step(ptr(Ainv), ptr(R), ptr(W), ptr(aux1), ptr(dual1), B, F,
+                                              N, float(rho), float(relaxation), _st()),
+               "admmbss_filter_step")
+    return W
+
+
+def _admm_slices(aux2, dual2, q):
+    assert tuple(aux2.shape) == tuple(dual2.shape)
+    aq, stride, shape = _dual_slice(aux2, q)
+    dq, _, _ = _dual_slice(dual2, q)
+    return aq, dq, stride, shape
+
+
+def admmbss_bin_norms(X, W, aux2, dual2, q, relaxation, out=None):
+    """r2 (B, N, T): sum over bins of |relaxation W x + (1 - relaxation) aux2_q + dual2_q|^2."""
+    aq, dq, stride, (B, N, F, T) = _admm_slices(aux2, dual2, q)
+    if out is None:
+        out = dv.empty((B, N, T), dv.f64, X.device)
+    ws, ws_bytes = _scratch(_L().ssspy_admmbss_bin_norms_workspace_bytes(B, N, F, T), X.device)
+    _lib.check(_L().ssspy_admmbss_bin_norms(ptr(X), ptr(W), aq, dq, stride, float(relaxation),
+                                            ptr(out), B, N, F, T, ptr(ws), ws_bytes, _st()),
+               "admmbss_bin_norms")
+    return out
+
+
+def admmbss_aux_step(X, W, aux2, dual2, q, kind, step_size, relaxation, r2=None, given=None):
+    """aux2_q <- prox(Z, step_size) by _lib.PROX_*, dual2_q <- Z - aux2_q, in place."""
+    aq, dq, stride, (B, N, F, T) = _admm_slices(aux2, dual2, q)
+    assert given is None or tuple(given.shape) == (B, N, F, T)
+    assert r2 is None or tuple(r2.shape) == (B, N, T)
+    _lib.check(_L().ssspy_admmbss_aux_step(ptr(X), ptr(W), aq, dq, stride, int(kind),
+                                           float(step_size), float(relaxation), ptr(r2), ptr(given),
+                                           B, N, F, T, _st()), "admmbss_aux_step")
+    return aux2, dual2
+
+
+def admmbss_form_z(X, W, aux2, dual2, q, relaxation, out=None):
+    """Z = relaxation W x + (1 - relaxation) aux2_q + dual2_q, (B, N, F, T)."""
+    aq, dq, stride, (B, N, F, T) = _admm_slices(aux2, dual2, q)
+    if out is None:
+        out = dv.empty((B, N, F, T), dv.c128, X.device)
+    _lib.check(_L().ssspy_admmbss_form_z(ptr(X), ptr(W), aq, dq, stride, float(relaxation), ptr(out),
+                                         B, N, F, T, _st()), "admmbss_form_z")
+    return out
+
+
 # ------------------------------------------------------------------------------ HVA
 def hva_route(F, route=_lib.HVA_ROUTE_AUTO):
     """The transform route (_lib.HVA_ROUTE_FFT / _DIRECT) the cepstral pass takes for F bins when

@@ -1,4 +1,5 @@
-from . import base, cacgmm, fdica, hva, ilrma, ipsdta, iva, mnmf, pdsbss, proxbss
+from . import admmbss, base, cacgmm, fdica, hva, ilrma, ipsdta, iva, mnmf, pdsbss, proxbss
+from .admmbss import ADMMBSS, ADMMBSSBase, MaskingADMMBSS
 from .base import IterativeMethodBase
 from .cacgmm import CACGMM, CACGMMBase
 from .fdica import (
@@ -19,5 +20,6 @@ from .proxbss import ProxBSSBase
 __all__ = ["IterativeMethodBase", "CACGMM", "CACGMMBase", "IPSDTABase", "BlockDecompositionIPSDTABase",
            "GaussIPSDTA", "TIPSDTA", "FDICABase", "GradFDICABase", "GradFDICA", "NaturalGradFDICA",
            "AuxFDICA", "GradLaplaceFDICA", "NaturalGradLaplaceFDICA", "AuxLaplaceFDICA",
-           "ProxBSSBase", "PDSBSSBase", "PDSBSS", "MaskingPDSBSS", "MaskingPDSHVA", "HVA", "base", "cacgmm",
+           "ProxBSSBase", "PDSBSSBase", "PDSBSS", "MaskingPDSBSS", "MaskingPDSHVA", "HVA", "ADMMBSSBase", "ADMMBSS",
+           "MaskingADMMBSS", "admmbss", "base", "cacgmm",
            "fdica", "hva", "ilrma", "ipsdta", "iva", "mnmf", "pdsbss", "proxbss"]

@@ -19,7 +19,10 @@ take Python closures on the whole estimate and run a compatibility path (see ``G
 
 The fixed-point family (ssspy/bss/iva.py:409-550, :991-1400): ``FastIVA`` and ``FasterIVA`` on the
 whitened mixture with unitary filters (csrc/fast_iva.hip, see ``FastIVABase``).
-The PDS / ADMM IVA variants are out of scope.
+
+The proximal front ends (ssspy/bss/iva.py:2217-2338): ``PDSIVA`` and ``ADMMIVA``, thin subclasses of
+``PDSBSS`` and ``ADMMBSS`` whose default penalty is ``prox.l21`` over the bins, in the form the
+kernels of those classes apply themselves.
 """
 
 import functools
@@ -29,12 +32,15 @@ import numpy as np
 
 from .. import _device as dv
 from .. import _lib, _ops
+from ..linalg import prox
 from ..special.flooring import identity, max_flooring
 from ..utils.flooring import choose_flooring_fn, device_flooring, host_floor, require_device_floor
 from ..utils.select_pair import resolve_pairs, sequential_pair_selector
 from ._device_state import LossShares, Synced
 from ._filter_base import _IP1, _IP2, _IPA, _ISS1, _ISS2, DemixingFilterBase
+from .admmbss import ADMMBSS
 from .base import IterativeMethodBase
+from .pdsbss import PDSBSS
 
 __all__ = [
     "GradIVABase",
@@ -44,6 +50,8 @@ __all__ = [
     "FastIVA",
     "FasterIVA",
     "AuxIVA",
+    "PDSIVA",
+    "ADMMIVA",
     "GradLaplaceIVA",
     "GradGaussIVA",
     "NaturalGradLaplaceIVA",
@@ -1363,3 +1371,89 @@ class NaturalGradGaussIVA(_GradGaussMixin, NaturalGradIVA):
             record_loss=record_loss,
             reference_id=reference_id,
         )
+
+
+def _vector_penalty(contrast_fn, prox_penalty):
+    """(contrast_fn, prox_penalty, penalty_fn) of PDSIVA / ADMMIVA (ref: ssspy/bss/iva.py:2233-2262,
+    :2295-2324).  The default penalty is ``prox.l21`` over the bins as a ``functools.partial`` that
+    leaves ``step_size`` open (the reference wraps it in a local function): ``proxbss.device_prox``
+    recognises it, so the default classes run on the device."""
+    if contrast_fn is not None and prox_penalty is None:
+        raise ValueError("Set prox_penalty.")
+    if contrast_fn is None and prox_penalty is not None:
+        raise ValueError("Set contrast_fn.")
+    if contrast_fn is None:
+
+        def contrast_fn(y: np.ndarray) -> np.ndarray:
+            return np.linalg.norm(y, axis=1)
+
+        prox_penalty = functools.partial(prox.l21, axis2=1)
+
+    def penalty_fn(y: np.ndarray) -> float:
+        """Sum of contrast function; ``y`` is (n_sources, n_bins, n_frames)."""
+        G = contrast_fn(y)  # (n_sources, n_frames)
+        return np.sum(G, axis=(0, 1)).item()
+
+    return contrast_fn, prox_penalty, penalty_fn
+
+
+class PDSIVA(PDSBSS):
+    """IVA by primal-dual splitting (ref: ssspy/bss/iva.py:2217-2277)."""
+
+    def __init__(
+        self,
+        mu1: float = 1,
+        mu2: float = 1,
+        alpha: float = None,
+        relaxation: float = 1,
+        contrast_fn: Callable[[np.ndarray], np.ndarray] = None,
+        prox_penalty: Callable[[np.ndarray, float], np.ndarray] = None,
+        callbacks=None,
+        scale_restoration: Union[bool, str] = True,
+        record_loss: bool = True,
+        reference_id: int = 0,
+    ) -> None:
+        contrast_fn, prox_penalty, penalty_fn = _vector_penalty(contrast_fn, prox_penalty)
+        super().__init__(
+            mu1=mu1,
+            mu2=mu2,
+            alpha=alpha,
+            relaxation=relaxation,
+            penalty_fn=penalty_fn,
+            prox_penalty=prox_penalty,
+            callbacks=callbacks,
+            scale_restoration=scale_restoration,
+            record_loss=record_loss,
+            reference_id=reference_id,
+        )
+        self.contrast_fn = contrast_fn
+
+
+class ADMMIVA(ADMMBSS):
+    """IVA by the alternating direction method of multipliers (ref: ssspy/bss/iva.py:2280-2338)."""
+
+    def __init__(
+        self,
+        rho: float = 1,
+        alpha: float = None,
+        relaxation: float = 1,
+        contrast_fn: Callable[[np.ndarray], np.ndarray] = None,
+        prox_penalty: Callable[[np.ndarray, float], np.ndarray] = None,
+        callbacks=None,
+        scale_restoration: Union[bool, str] = True,
+        record_loss: bool = True,
+        reference_id: int = 0,
+    ) -> None:
+        contrast_fn, prox_penalty, penalty_fn = _vector_penalty(contrast_fn, prox_penalty)
+        super().__init__(
+            rho=rho,
+            alpha=alpha,
+            relaxation=relaxation,
+            penalty_fn=penalty_fn,
+            prox_penalty=prox_penalty,
+            callbacks=callbacks,
+            scale_restoration=scale_restoration,
+            record_loss=record_loss,
+            reference_id=reference_id,
+        )
+        self.contrast_fn = contrast_fn
