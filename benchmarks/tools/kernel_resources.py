@@ -38,6 +38,7 @@ def parse(text):
 
 def short(name):
     name = re.sub(r"HIP_vector_type<double, 2u>", "c128", name)
+    name = name.replace("(anonymous namespace)::", "")
     name = re.sub(r"\(.*", "", name)
     return name.replace("void ", "").replace("ssspy::", "")
 

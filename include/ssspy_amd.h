@@ -675,6 +675,70 @@ int ssspy_fdica_steps(const void *X, void *W, int B, int N, int F, int T, int al
                       int n_steps, double *loss_data, double *logdet, long long slot_stride,
                       int *info, void *stream);
 
+/* ------------------------------------------------------------- time-domain ICA (real fp64 waveforms) */
+
+/* `kind` of ssspy_ica_stats: the nonlinearity applied to y = W x in registers. */
+enum {
+  SSSPY_ICA_LAPLACE = 0,  /* G = |y|, phi = sign(y) (sign(0) = 0), phi' = 0                          */
+  SSSPY_ICA_LOGISTIC = 1, /* G = max(y,0) + log1p(exp(-|y|)), phi = 1 / (1 + exp(-y)), phi' = s(1-s) */
+  SSSPY_ICA_LOGCOSH = 2,  /* G = |y| + log1p(exp(-2|y|)) - log 2, phi = tanh(y), phi' = 1 - tanh^2   */
+  SSSPY_ICA_IDENTITY = 3, /* G = 0, phi = y, phi' = 0 (with W = I and right = X: the Gram matrix)    */
+  SSSPY_ICA_GIVEN = 4,    /* phi (and phi') are read from memory: the closures' route                */
+};
+
+/* `right` of ssspy_ica_stats: the right factor of the N x N sums. */
+enum {
+  SSSPY_ICA_RIGHT_Y = 0, /* sum_t phi(y_n) y_m (the gradient classes) */
+  SSSPY_ICA_RIGHT_X = 1, /* sum_t phi(y_n) x_m (FastICA; the Gram matrix) */
+};
+
+/* `algorithm` of ssspy_ica_step. */
+enum {
+  SSSPY_ICA_FOLD_ONLY = 0,    /* fold the records (means, loss terms), leave W alone */
+  SSSPY_ICA_GRAD = 1,         /* W <- W - eta D W^-T, LU with partial pivoting        */
+  SSSPY_ICA_NATURAL_GRAD = 2, /* W <- W - eta D W                                     */
+  SSSPY_ICA_FAST = 3,         /* fixed point, Gram-Schmidt in row order, unit rows    */
+};
+
+/* Samples of one partial record of ssspy_ica_stats.  A function of the shape only (today a constant),
+ * never of the device: the records, and so every bit of the result, are the same on every run.
+ * Host only. */
+int ssspy_ica_chunk_samples(int N, long long T);
+
+/* Bytes of the workspace ssspy_ica_stats fills and ssspy_ica_step folds: one record of
+ * N N + 2 N doubles per (mixture, chunk).  0 on a bad argument.  Host only. */
+size_t ssspy_ica_workspace_bytes(int B, int N, long long T);
+
+/* The statistics pass.  X (B,N,T) real fp64 waveforms, W (B,N,N).  Lanes take consecutive samples
+ * (coalesced loads of every channel row), form y = W x, apply the nonlinearity `kind` in registers
+ * and add up, per (mixture, chunk), the record
+ *   [n N + m]   sum_t phi(y_n) r_m   (r = y or x, `right`)
+ *   [N N + n]   sum_t G(y_n)
+ *   [N N + N + n] sum_t phi'(y_n)
+ * at ws + (b chunks + chunk) (N N + 2 N).  y and phi never reach memory.  kind == SSSPY_ICA_GIVEN:
+ * phi (B,N,T) is read instead (dphi (B,N,T) too when not NULL; G = 0).  Lane -> wave (butterfly) ->
+ * workgroup (waves in order): a fixed order, no atomics.  2..8 sources compiled per count, 9..16
+ * with the count at run time and the rows in groups of four (grid z), so that no lane holds more
+ * than 80 accumulators.  SSSPY_ERR_UNSUPPORTED outside 2..16 sources and above 65535 mixtures.
+ * replaces: ssspy/bss/ica.py:536-539, :691-694, :825-827 and the data term of :171-175, :397-401. */
+int ssspy_ica_stats(const double *X, const double *W, const double *phi, const double *dphi,
+                    void *ws, size_t ws_bytes, int B, int N, long long T, int kind, int right,
+                    void *stream);
+
+/* The step, one wave per mixture: adds the chunk records of ws in chunk order, divides by T, and
+ * updates W (B,N,N) in place by `algorithm`.  loss_data (B, may be NULL): sum_n mean_t G(y_n) of
+ * the state the records were formed from; logdet (B, may be NULL): log|det W| of that state (-inf
+ * for a singular one); means (B, N N + 2 N, may be NULL): the folded record over T.  SSSPY_ICA_GRAD
+ * bumps info[0] and leaves W alone where a pivot is exactly zero (numpy.linalg.inv raises there).
+ * replaces: ssspy/bss/ica.py:540-549, :695-702, :826-836, :191. */
+int ssspy_ica_step(const void *ws, size_t ws_bytes, double *W, int B, int N, long long T,
+                   int algorithm, int holonomic, double step_size, double *loss_data,
+                   double *logdet, double *means, int *info, void *stream);
+
+/* Y (B,N,T) = W (B,N,N) X (B,N,T), real fp64 (ssspy/bss/ica.py:152, :379; whitening: W = P). */
+int ssspy_ica_separate(const double *X, const double *W, double *Y, int B, int N, long long T,
+                       void *stream);
+
 /* ------------------------------------------------- PDSBSS (primal-dual splitting), prox of -log|det| */
 
 /* prox_{-step_size log|det|}(X) = U diag(f(sigma)) V^H, f(s) = (s + sqrt(s^2 + 4 step_size)) / 2, for n

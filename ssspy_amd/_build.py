@@ -48,6 +48,7 @@ def _units():
         ("grad_iva.hip", "grad_iva.o", []),
         ("fast_iva.hip", "fast_iva.o", []),
         ("fdica.hip", "fdica.o", []),
+        ("ica.hip", "ica.o", []),
         ("pdsbss.hip", "pdsbss.o", []),
         ("hva.hip", "hva.o", []),
         ("admmbss.hip", "admmbss.o", []),

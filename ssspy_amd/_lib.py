@@ -45,6 +45,11 @@ GMNMF_BASIS_REGISTERS, GMNMF_BASIS_LDS_TILE, GMNMF_BASIS_MEMORY = range(3)
 # SSSPY_FDICA_*: `algorithm` of the FDICA entry points; SSSPY_FDICA_ROUTE_*: what ssspy_fdica_route returns
 FDICA_GRAD, FDICA_NATURAL_GRAD, FDICA_AUX_IP1, FDICA_AUX_IP2 = range(4)
 FDICA_ROUTE_RESIDENT, FDICA_ROUTE_STREAMING, FDICA_ROUTE_COMPOSED = range(3)
+# SSSPY_ICA_*: `kind`, `right` of ssspy_ica_stats and `algorithm` of ssspy_ica_step
+ICA_LAPLACE, ICA_LOGISTIC, ICA_LOGCOSH, ICA_IDENTITY, ICA_GIVEN = range(5)
+ICA_RIGHT_Y, ICA_RIGHT_X = range(2)
+ICA_FOLD_ONLY, ICA_GRAD, ICA_NATURAL_GRAD, ICA_FAST = range(4)
+ICA_MIN_SOURCES = 2
 # SSSPY_PROX_*: `kind` of ssspy_pdsbss_dual_step
 PROX_L1, PROX_L21_SOURCES, PROX_L21_BINS, PROX_L21_FRAMES, PROX_MASK, PROX_GIVEN = range(6)
 # SSSPY_HVA_ROUTE_*: `route` of the HVA entry points and what ssspy_hva_route returns
@@ -145,6 +150,11 @@ PROTOTYPES = {
     "ssspy_fdica_weight": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _d, _p, _q, _p]),
     "ssspy_fdica_route": (_i, [_i, _i, _i, _i, _i]),
     "ssspy_fdica_steps": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _d, _i, _d, _i, _p, _p, _q, _p, _p]),
+    "ssspy_ica_chunk_samples": (_i, [_i, _q]),
+    "ssspy_ica_workspace_bytes": (_z, [_i, _i, _q]),
+    "ssspy_ica_stats": (_i, [_p, _p, _p, _p, _p, _z, _i, _i, _q, _i, _i, _p]),
+    "ssspy_ica_step": (_i, [_p, _z, _p, _i, _i, _q, _i, _i, _d, _p, _p, _p, _p, _p]),
+    "ssspy_ica_separate": (_i, [_p, _p, _p, _i, _i, _q, _p]),
     "ssspy_prox_neg_logdet": (_i, [_p, _p, _q, _i, _d, _p]),
     "ssspy_pdsbss_contract": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "ssspy_pdsbss_filter_step": (_i, [_p, _p, _p, _i, _i, _i, _d, _d, _d, _p]),

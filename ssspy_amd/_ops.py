@@ -763,6 +763,53 @@ def fdica_steps(X, W, algorithm, holonomic, step_size, flooring, n_steps, info, 
     return W
 
 
+# ------------------------------------------------------------------------------ time-domain ICA
+def ica_chunk_samples(N, T):
+    """Samples per partial record of the statistics pass (a function of the shape only)."""
+    return int(_L().ssspy_ica_chunk_samples(int(N), int(T)))
+
+
+def ica_workspace(B, N, T, dev):
+    """(buffer, bytes) for the records of ``ica_stats`` on a (B, N, T) problem."""
+    nbytes = int(_L().ssspy_ica_workspace_bytes(int(B), int(N), int(T)))
+    if nbytes == 0:
+        raise ValueError("ica_workspace: bad shape ({}, {}, {})".format(B, N, T))
+    return _workspace(nbytes, dev)
+
+
+def ica_stats(X, W, ws, kind, right, phi=None, dphi=None):
+    """The statistics pass on X (B, N, T) f64 with the filters W (B, N, N): one record per (mixture,
+    chunk) into ``ws`` = (buffer, bytes).  ``phi`` / ``dphi`` (B, N, T): only with ICA_GIVEN."""
+    B, N, T = X.shape
+    assert tuple(W.shape) == (B, N, N)
+    assert phi is None or tuple(phi.shape) == (B, N, T)
+    assert dphi is None or tuple(dphi.shape) == (B, N, T)
+    _lib.check(_L().ssspy_ica_stats(ptr(X), ptr(W), ptr(phi), ptr(dphi), ptr(ws[0]), ws[1], B, N, T,
+                                    int(kind), int(right), _st()), "ica_stats")
+
+
+def ica_step(ws, W, T, algorithm, holonomic=False, step_size=0.0, loss_data=None, logdet=None,
+             means=None, info=None):
+    """Fold the records of ``ws`` and update W (B, N, N) in place by ``algorithm``; the loss terms of
+    the state the records were formed from go to ``loss_data`` / ``logdet`` (B,), the folded record
+    over T to ``means`` (B, N N + 2 N)."""
+    B, N = W.shape[0], W.shape[1]
+    _lib.check(_L().ssspy_ica_step(ptr(ws[0]), ws[1], ptr(W), B, N, int(T), int(algorithm),
+                                   int(bool(holonomic)), float(step_size), ptr(loss_data),
+                                   ptr(logdet), ptr(means), ptr(info), _st()), "ica_step")
+    return W
+
+
+def ica_separate(X, W, out=None):
+    """Y (B, N, T) = W (B, N, N) X (B, N, T), real f64."""
+    B, N, T = X.shape
+    assert tuple(W.shape) == (B, N, N)
+    if out is None:
+        out = dv.empty((B, N, T), dv.f64, X.device)
+    _lib.check(_L().ssspy_ica_separate(ptr(X), ptr(W), ptr(out), B, N, T, _st()), "ica_separate")
+    return out
+
+
 # ------------------------------------------------------------------------------ PDSBSS
 def prox_neg_logdet(X, step_size, out=None):
     """prox of -step_size log|det| of the matrices X (..., N, N), a device tensor."""

@@ -27,6 +27,10 @@ _DEFAULTS = {
     # ssspy_fdica_route allows; False: the per-iteration operators (what IP2, user closures, host
     # floors and 9..16 sources run)
     "fdica_kernel": True,
+    # time-domain ICA applies a named nonlinearity (bss.ica.NAMED: laplace, logistic, logcosh passed
+    # as themselves) inside the statistics pass; False: the compatibility route every other callable
+    # takes (Y down, Phi up once per iteration; bss.ica.route decides, once per call)
+    "ica_named": True,
 }
 VALUES = dict(_DEFAULTS)  # (tests: monkeypatch.setitem(_routes.VALUES, "implied_filter", False))
 

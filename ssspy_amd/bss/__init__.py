@@ -1,4 +1,4 @@
-from . import admmbss, base, cacgmm, fdica, hva, ilrma, ipsdta, iva, mnmf, pdsbss, proxbss
+from . import admmbss, base, cacgmm, fdica, hva, ica, ilrma, ipsdta, iva, mnmf, pdsbss, proxbss
 from .admmbss import ADMMBSS, ADMMBSSBase, MaskingADMMBSS
 from .base import IterativeMethodBase
 from .cacgmm import CACGMM, CACGMMBase
@@ -13,6 +13,7 @@ from .fdica import (
     NaturalGradLaplaceFDICA,
 )
 from .hva import HVA, MaskingPDSHVA
+from .ica import FastICA, GradICA, GradLaplaceICA, NaturalGradICA, NaturalGradLaplaceICA
 from .ipsdta import TIPSDTA, BlockDecompositionIPSDTABase, GaussIPSDTA, IPSDTABase
 from .pdsbss import PDSBSS, MaskingPDSBSS, PDSBSSBase
 from .proxbss import ProxBSSBase
@@ -21,5 +22,6 @@ __all__ = ["IterativeMethodBase", "CACGMM", "CACGMMBase", "IPSDTABase", "BlockDe
            "GaussIPSDTA", "TIPSDTA", "FDICABase", "GradFDICABase", "GradFDICA", "NaturalGradFDICA",
            "AuxFDICA", "GradLaplaceFDICA", "NaturalGradLaplaceFDICA", "AuxLaplaceFDICA",
            "ProxBSSBase", "PDSBSSBase", "PDSBSS", "MaskingPDSBSS", "MaskingPDSHVA", "HVA", "ADMMBSSBase", "ADMMBSS",
-           "MaskingADMMBSS", "admmbss", "base", "cacgmm",
-           "fdica", "hva", "ilrma", "ipsdta", "iva", "mnmf", "pdsbss", "proxbss"]
+           "MaskingADMMBSS", "GradICA", "NaturalGradICA", "FastICA", "GradLaplaceICA",
+           "NaturalGradLaplaceICA", "admmbss", "base", "cacgmm",
+           "fdica", "hva", "ica", "ilrma", "ipsdta", "iva", "mnmf", "pdsbss", "proxbss"]
