@@ -297,8 +297,9 @@ int ssspy_solve(const void *A, const void *Bm, void *X, long long n, int N, int 
 /* closed-form 2x2 inverse.  replaces: ssspy/linalg/inv.py:4-54 (inv2). */
 int ssspy_inv2(const void *A, void *out, long long n, void *stream);
 
-/* Hermitian eigen-decomposition (cyclic complex Jacobi): lamb (n,M) ascending, V (n,M,M) unit
- * eigenvectors in columns (phase convention differs from LAPACK; A V = V diag(lamb) holds).
+/* Hermitian eigen-decomposition (cyclic complex Jacobi) of the Hermitian part (A + A^H) / 2 at every
+ * size: lamb (n,M) ascending, V (n,M,M) unit eigenvectors in columns (phase convention differs from
+ * LAPACK; A V = V diag(lamb) holds).
  * M = 2 (and ssspy_eigh2 below): the eigenvectors carry the phases reference LAPACK's zheevd gives
  * them (zhetd2 + dlaev2, restated in csrc/eigh2.hpp) -- what np.linalg.eigh returns in the
  * reference's eigh2 and pairwise updates (ssspy/linalg/eigh.py:155-157, :198).
@@ -1300,6 +1301,10 @@ int ssspy_gmnmf_separate(const void *X, const double *basis, const double *activ
 /* ------------------------------------------------------------------ Hermitian matrix functions
  * One matrix per lane, M in [2, 16] (9 .. 16: the size at run time, csrc/hermitian_rt.hip); arrays
  * flattened to (n, M, M) c128.
+ * Tested magnitude range (these, ssspy_eigh, ssspy_to_psd and ssspy_solve): entries from 2^-240 to
+ * 2^240 for the one-matrix entry points and from 2^-120 to 2^120 for those that take two matrices, so
+ * that every square and pairwise product the kernels form stays inside [1e-300, 1e300], the range the
+ * Jacobi rotation and the Cholesky pivots assume (tests/test_gpu_linalg_elementwise.py).
  * generalised eigh through the Cholesky factor of B, eigenvalues ascending -> lamb (n, M), Z (n, M, M):
  *   type 1: A z = lamb B z; 2: A B z = lamb z; 3: B A z = lamb z.   replaces: ssspy/linalg/eigh.py:8-81, :164-207 */
 int ssspy_eigh_general(const void *A, const void *Bm, double *lamb, void *Z, long long n, int M,

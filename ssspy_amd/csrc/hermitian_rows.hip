@@ -124,6 +124,10 @@ __global__ __launch_bounds__(256, 2) void k_eigh_rows(const c128 *__restrict__ A
   } else {
     c128 out[8];
     rebuild(w, q.r < M ? apply_floor(lam, floor_kind, eps) : 0.0, q.X, q.r, out);
+    // (the rows are rebuilt lane by lane, each with its own rounding: Hermitise last, as to_psd is
+    //  defined and as the lane-per-matrix kernels do)
+    hermitize_rows(out, q.X, q.r);
+    put(out, q.r, cmake(sel(out, q.r).x, 0.0));
     store_rows(V, q.idx, M, out, q.r, q.live);
   }
 }
@@ -143,6 +147,8 @@ __global__ __launch_bounds__(256, 2) void k_sqrtmh_rows(const c128 *__restrict__
   const double f = mode == 0 ? s : 1.0 / apply_floor(s, floor_kind, eps);
   c128 res[8];
   rebuild(w, q.r < M ? f : 0.0, q.X, q.r, res);
+  hermitize_rows(res, q.X, q.r);  // exactly Hermitian, as herm_rebuild of the lane-per-matrix kernels
+  put(res, q.r, cmake(sel(res, q.r).x, 0.0));
   store_rows(out, q.idx, M, res, q.r, q.live);
 }
 

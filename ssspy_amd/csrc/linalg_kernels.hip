@@ -283,14 +283,17 @@ __global__ __launch_bounds__(256) void k_eigh2(const c128 *__restrict__ A, const
 }
 
 // plain 2 x 2 Hermitian eigh with np.linalg.eigh's eigenvector phases (the reference's eigh2 without B
-// IS np.linalg.eigh, ssspy/linalg/eigh.py:155-157): lower triangle, eigh2_lapack
+// IS np.linalg.eigh, ssspy/linalg/eigh.py:155-157): eigh2_lapack on the lower triangle of the
+// Hermitian part, as every other size takes it (for a Hermitian input: the lower triangle itself, bit
+// for bit)
 __global__ __launch_bounds__(256) void k_eigh2_plain(const c128 *__restrict__ A, double *lamb,
                                                      c128 *V, long long n) {
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= n) return;
   double ev[2];
   c128 P[2][2];
-  eigh2_lapack(A[idx * 4].x, A[idx * 4 + 3].x, A[idx * 4 + 2], ev, P);
+  const c128 up = A[idx * 4 + 1], lo = A[idx * 4 + 2];
+  eigh2_lapack(A[idx * 4].x, A[idx * 4 + 3].x, cmake(0.5 * (lo.x + up.x), 0.5 * (lo.y - up.y)), ev, P);
   lamb[idx * 2] = ev[0];
   lamb[idx * 2 + 1] = ev[1];
   V[idx * 4] = P[0][0];
