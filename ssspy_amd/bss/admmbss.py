@@ -34,7 +34,6 @@ import numpy as np
 from .. import _device as dv
 from .. import _lib, _ops
 from ._device_state import Synced
-from .base import IterativeMethodBase
 from .proxbss import ProxBSSBase, device_prox
 
 __all__ = ["ADMMBSS", "MaskingADMMBSS"]
@@ -47,8 +46,7 @@ class ADMMBSSBase(ProxBSSBase):
     auxiliary1 = Synced(dv.c128)
     dual1 = Synced(dv.c128)
     auxiliary2 = Synced(dv.c128)
-    dual2 = Synced(dv.c128)
-    _aux2_rank = 5  # (B, Q, N, F, T)
+    dual2 = Synced(dv.c128)  # (these two (B, Q, N, F, T); (B, N, F, T) for the masking class)
 
     def __repr__(self) -> str:
         s = "ADMMBSS("
@@ -62,24 +60,7 @@ class ADMMBSSBase(ProxBSSBase):
 
     def _init_steps(self, rho, alpha, relaxation) -> None:
         self.rho = rho
-        if alpha is None:
-            self.relaxation = relaxation
-        else:
-            assert relaxation == 1, "You cannot specify relaxation and alpha simultaneously."
-            warnings.warn("alpha is deprecated. Set relaxation instead.", DeprecationWarning)
-            self.relaxation = alpha
-
-    def _run(self, input, n_iter, initial_call, kwargs):
-        """ref: ssspy/bss/admmbss.py:121-151, :342-355."""
-        self._bind_input(input)
-        self._reset(**kwargs)
-        IterativeMethodBase.__call__(self, n_iter=n_iter, initial_call=initial_call)
-        return self._finish_call()
-
-    def _state_shapes(self):
-        B, N, F, T = self._X.shape
-        aux2 = (B, self.n_penalties, N, F, T) if self._aux2_rank == 5 else (B, N, F, T)
-        return {"auxiliary1": (B, F, N, N), "dual1": (B, F, N, N), "auxiliary2": aux2, "dual2": aux2}
+        self._init_relaxation(alpha, relaxation)
 
     def _reset(self, **kwargs) -> None:
         """ref: ssspy/bss/admmbss.py:168-218, :357-408."""
@@ -89,29 +70,13 @@ class ADMMBSSBase(ProxBSSBase):
                               DeprecationWarning)
                 kwargs[new] = kwargs.pop(old)
         super()._reset(**kwargs)
-        dev = self._X.device
-        for name, shape in self._state_shapes().items():
-            if not self._state_has(name):
-                self._state_set_dev(name, dv.zeros(shape, dv.c128, dev))
-            elif not self._state_is_none(name):
-                # (a copy: a state given by keyword is not overwritten)
-                setattr(self, name, np.array(getattr(self, name), dtype=np.complex128, copy=True))
-            if self._state_is_none(name):
-                raise ValueError("{}=None cannot be given at reset.".format(name))
-            got = tuple(self._state_dev(name).shape)
-            if got != shape:
-                skip = 0 if self._batched else 1
-                raise ValueError("{} must have shape {}, got {}.".format(name, shape[skip:],
-                                                                         got[skip:]))
         B, N, F, T = self._X.shape
+        aux2 = self._penalty_state_shape()
+        self._reset_states({"auxiliary1": (B, F, N, N), "dual1": (B, F, N, N), "auxiliary2": aux2,
+                            "dual2": aux2})
         # (Q conj(X) X^T + I)^-1 per bin: constant over the iterations of this call
         self._Ainv = _ops.admmbss_gram_inverse(self._X, self.n_penalties)
-        self._R = dv.empty((B, F, N, N), dv.c128, dev)
-
-    def _state5(self, name):
-        """auxiliary2 / dual2 as (B, Q, N, F, T) (a view for the masking class)."""
-        state = self._state_dev(name)
-        return state if state.dim() == 5 else state.unsqueeze(1)
+        self._R = dv.empty((B, F, N, N), dv.c128, self._X.device)
 
     def _filter_step(self):
         """The contraction and the filter step: returns (W, auxiliary2, dual2), the last two as
@@ -147,12 +112,8 @@ class ADMMBSSBase(ProxBSSBase):
         W = self._state_dev("demix_filter")
         Y = _ops.separate(self._X, W)
         self._check_device_errors()
-        values = []
-        for Yb, Wb in zip(dv.to_host(Y), dv.to_host(W)):
-            penalty = 0
-            for penalty_fn in self._penalty_fns():
-                penalty = penalty + penalty_fn(Yb)
-            values.append(penalty - np.sum(self.compute_logdet(Wb)))
+        values = [penalty - np.sum(self.compute_logdet(Wb))
+                  for penalty, Wb in zip(self._host_penalties(Y), dv.to_host(W))]
         return self._loss_entry(np.asarray(values, dtype=np.float64).reshape(-1))
 
 
@@ -216,11 +177,7 @@ class ADMMBSS(ADMMBSSBase):
             kind = device_prox(prox_penalty)
             if kind is None:
                 # the compatibility path: the callable on the host, once per mixture
-                Z = self._host_z(W, aux2, dual2, q)
-                V = np.stack([np.asarray(prox_penalty(Zb, step_size=step_size)) for Zb in Z])
-                if V.shape != Z.shape:
-                    raise ValueError("prox_penalty must map (n_sources, n_bins, n_frames) to the "
-                                     "same shape.")
+                V = self._host_prox(self._host_z(W, aux2, dual2, q), prox_penalty, step_size)
                 self._given_step(W, aux2, dual2, q, _lib.PROX_GIVEN, V)
                 continue
             r2 = None
@@ -242,7 +199,7 @@ class MaskingADMMBSS(ADMMBSSBase):
     callable and raises there).
     """
 
-    _aux2_rank = 4  # (B, N, F, T)
+    _masking = True
 
     def __init__(
         self,
@@ -256,17 +213,8 @@ class MaskingADMMBSS(ADMMBSSBase):
         record_loss: Optional[bool] = None,
         reference_id: int = 0,
     ) -> None:
-        self._init_iterative(callbacks, record_loss)
-        if penalty_fn is None:
-            assert not record_loss, "To record loss, set penalty_fn."
-        else:
-            assert callable(penalty_fn), "penalty_fn should be callable."
-        if mask_fn is None:
-            raise ValueError("Specify masking function.")
-        assert callable(mask_fn), "mask_fn should be callable."
-        self.penalty_fn = penalty_fn
-        self.mask_fn = mask_fn
-        self._init_scale(scale_restoration, reference_id)
+        self._init_masking(penalty_fn, mask_fn, callbacks, scale_restoration, record_loss,
+                           reference_id)
         self._init_steps(rho, alpha, relaxation)
 
     def __call__(
@@ -275,20 +223,11 @@ class MaskingADMMBSS(ADMMBSSBase):
         """Separate a frequency-domain multichannel mixture (ref: ssspy/bss/admmbss.py:342-355)."""
         return self._run(input, n_iter, initial_call, kwargs)
 
-    @property
-    def n_penalties(self):
-        """Number of penalty terms."""
-        return 1
-
-    def _penalty_fns(self):
-        return [self.penalty_fn]
-
     def update_once(self) -> None:
         """Update demixing filters, auxiliary parameters, and dual parameters once
         (ref: ssspy/bss/admmbss.py:415-442)."""
         W, aux2, dual2 = self._filter_step()
-        Z = self._host_z(W, aux2, dual2, 0)
-        mask = np.stack([np.broadcast_to(np.asarray(self.mask_fn(Zb)), Zb.shape) for Zb in Z])
+        mask = self._host_mask_fn(self._host_z(W, aux2, dual2, 0))
         self._given_step(W, aux2, dual2, 0, _lib.PROX_MASK, mask)
         self._state_touch("auxiliary2")
         self._state_touch("dual2")

@@ -21,7 +21,6 @@ Extension over the reference: ``(n_mixtures, n_channels, n_bins, n_frames)`` inp
 ``dual`` then carries the same leading axis.  2..16 sources.
 """
 
-import warnings
 from typing import Callable, List, Optional, Union
 
 import numpy as np
@@ -29,7 +28,6 @@ import numpy as np
 from .. import _device as dv
 from .. import _lib, _ops
 from ._device_state import Synced
-from .base import IterativeMethodBase
 from .proxbss import ProxBSSBase, device_prox
 
 __all__ = ["PDSBSSBase", "PDSBSS", "MaskingPDSBSS"]
@@ -39,8 +37,7 @@ class PDSBSSBase(ProxBSSBase):
     """Base class of blind source separation via proximal splitting algorithm
     (ref: ssspy/bss/pdsbss.py:14-55).  ``record_loss=None`` records no loss, see ``ProxBSSBase``."""
 
-    dual = Synced(dv.c128)
-    _dual_rank = 5  # (B, Q, N, F, T)
+    dual = Synced(dv.c128)  # (B, Q, N, F, T); (B, N, F, T) for the masking class
 
     def __repr__(self) -> str:
         s = "PDSBSS("
@@ -54,52 +51,20 @@ class PDSBSSBase(ProxBSSBase):
 
     def _init_steps(self, mu1, mu2, alpha, relaxation) -> None:
         self.mu1, self.mu2 = mu1, mu2
-        if alpha is None:
-            self.relaxation = relaxation
-        else:
-            assert relaxation == 1, "You cannot specify relaxation and alpha simultaneously."
-            warnings.warn("alpha is deprecated. Set relaxation instead.", DeprecationWarning)
-            self.relaxation = alpha
-
-    def _run(self, input, n_iter, initial_call, kwargs):
-        """ref: ssspy/bss/pdsbss.py:126-156, :320-350."""
-        self._bind_input(input)
-        self._reset(**kwargs)
-        IterativeMethodBase.__call__(self, n_iter=n_iter, initial_call=initial_call)
-        return self._finish_call()
-
-    def _dual_shape(self):
-        B, N, F, T = self._X.shape
-        return (B, self.n_penalties, N, F, T) if self._dual_rank == 5 else (B, N, F, T)
+        self._init_relaxation(alpha, relaxation)
 
     def _reset(self, **kwargs) -> None:
         """ref: ssspy/bss/pdsbss.py:173-195, :366-389."""
         super()._reset(**kwargs)
-        shape = self._dual_shape()
-        if not self._state_has("dual"):
-            self._state_set_dev("dual", dv.zeros(shape, dv.c128, self._X.device))
-        elif not self._state_is_none("dual"):
-            # (a copy: the dual variable given by keyword is not overwritten)
-            self.dual = np.array(self.dual, dtype=np.complex128, copy=True)
-        if self._state_is_none("dual"):
-            raise ValueError("dual=None cannot be given at reset.")
-        if tuple(self._state_dev("dual").shape) != shape:
-            raise ValueError("dual must have shape {}, got {}.".format(
-                shape if self._batched else shape[1:],
-                tuple(self._state_dev("dual").shape)[0 if self._batched else 1:]))
+        self._reset_states({"dual": self._penalty_state_shape()})
         B, N, F, T = self._X.shape
         dev = self._X.device
         self._XY = dv.empty((B, F, N, N), dv.c128, dev)
         self._W2 = dv.empty((B, F, N, N), dv.c128, dev)
 
-    def _dual5(self):
-        """The dual variable as (B, Q, N, F, T) (a view for the masking class)."""
-        dual = self._state_dev("dual")
-        return dual if dual.dim() == 5 else dual.unsqueeze(1)
-
     def _filter_step(self):
         """Steps (a) and (b): returns (dual (B,Q,N,F,T), the filter 2 Wt - W of the dual step)."""
-        dual = self._dual5()
+        dual = self._state5("dual")
         W = self._state_dev("demix_filter")
         _ops.pdsbss_contract(dual, self._X, out=self._XY)
         _ops.pdsbss_filter_step(W, self._XY, self._W2, self.mu1, self.mu2, self.relaxation)
@@ -111,6 +76,11 @@ class PDSBSSBase(ProxBSSBase):
         Z = _ops.pdsbss_form_z(self._X, W2, dual, q)
         self._check_device_errors()
         return dv.to_host(Z)
+
+    def _given_step(self, dual, W2, q, kind, values) -> None:
+        """The dual step with what the host formed from Z (Yt or the mask)."""
+        aux = dv.to_device(values, dtype=np.complex128, dev=self._X.device)
+        _ops.pdsbss_dual_step(self._X, W2, dual, q, kind, 1 / self.mu2, self.relaxation, aux=aux)
 
 
 class PDSBSS(PDSBSSBase):
@@ -172,13 +142,8 @@ class PDSBSS(PDSBSSBase):
             if kind is None:
                 # the compatibility path: the callable on the host, once per mixture
                 Z = self._host_z(dual, W2, q)
-                Yt = np.stack([Zb - np.asarray(prox_penalty(Zb, step_size=step_size)) for Zb in Z])
-                if Yt.shape != Z.shape:
-                    raise ValueError("prox_penalty must map (n_sources, n_bins, n_frames) to the "
-                                     "same shape.")
-                aux = dv.to_device(Yt, dtype=np.complex128, dev=self._X.device)
-                _ops.pdsbss_dual_step(self._X, W2, dual, q, _lib.PROX_GIVEN, step_size,
-                                      self.relaxation, aux=aux)
+                Yt = self._host_prox(Z, prox_penalty, step_size, residual=True)
+                self._given_step(dual, W2, q, _lib.PROX_GIVEN, Yt)
                 continue
             r2 = None
             if kind == _lib.PROX_L21_BINS:
@@ -197,7 +162,7 @@ class MaskingPDSBSS(PDSBSSBase):
     callable and raises there).
     """
 
-    _dual_rank = 4  # (B, N, F, T)
+    _masking = True
 
     def __init__(
         self,
@@ -212,17 +177,8 @@ class MaskingPDSBSS(PDSBSSBase):
         record_loss: Optional[bool] = None,
         reference_id: int = 0,
     ) -> None:
-        self._init_iterative(callbacks, record_loss)
-        if penalty_fn is None:
-            assert not record_loss, "To record loss, set penalty_fn."
-        else:
-            assert callable(penalty_fn), "penalty_fn should be callable."
-        if mask_fn is None:
-            raise ValueError("Specify masking function.")
-        assert callable(mask_fn), "mask_fn should be callable."
-        self.penalty_fn = penalty_fn
-        self.mask_fn = mask_fn
-        self._init_scale(scale_restoration, reference_id)
+        self._init_masking(penalty_fn, mask_fn, callbacks, scale_restoration, record_loss,
+                           reference_id)
         self._init_steps(mu1, mu2, alpha, relaxation)
 
     def __call__(
@@ -242,20 +198,9 @@ class MaskingPDSBSS(PDSBSSBase):
         s += ")"
         return s.format(**self.__dict__)
 
-    @property
-    def n_penalties(self):
-        """Number of penalty terms."""
-        return 1
-
-    def _penalty_fns(self):
-        return [self.penalty_fn]
-
     def update_once(self) -> None:
         """Update demixing filters and dual parameters once (ref: ssspy/bss/pdsbss.py:396-412)."""
         dual, W2 = self._filter_step()
-        Z = self._host_z(dual, W2, 0)
-        mask = np.stack([np.broadcast_to(np.asarray(self.mask_fn(Zb)), Zb.shape) for Zb in Z])
-        aux = dv.to_device(mask, dtype=np.complex128, dev=self._X.device)
-        _ops.pdsbss_dual_step(self._X, W2, dual, 0, _lib.PROX_MASK, 1 / self.mu2, self.relaxation,
-                              aux=aux)
+        mask = self._host_mask_fn(self._host_z(dual, W2, 0))
+        self._given_step(dual, W2, 0, _lib.PROX_MASK, mask)
         self._state_touch("dual")

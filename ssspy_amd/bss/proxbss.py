@@ -8,6 +8,7 @@ other demixing-filter separators (``DemixingFilterBase``).
 """
 
 import functools
+import warnings
 from typing import Callable, List, Optional, Union
 
 import numpy as np
@@ -85,6 +86,32 @@ class ProxBSSBase(DemixingFilterBase):
             ), "Length of penalty_fn and prox_penalty are different."
         self._init_scale(scale_restoration, reference_id)
 
+    _masking = False  # (the masking classes: one penalty, its state without the penalty axis)
+
+    def _init_masking(self, penalty_fn, mask_fn, callbacks, scale_restoration, record_loss,
+                      reference_id) -> None:
+        """The constructor of a masking class: ``mask_fn`` in the place of ``prox_penalty``."""
+        self._init_iterative(callbacks, record_loss)
+        if penalty_fn is None:
+            assert not record_loss, "To record loss, set penalty_fn."
+        else:
+            assert callable(penalty_fn), "penalty_fn should be callable."
+        if mask_fn is None:
+            raise ValueError("Specify masking function.")
+        assert callable(mask_fn), "mask_fn should be callable."
+        self.penalty_fn = penalty_fn
+        self.mask_fn = mask_fn
+        self._init_scale(scale_restoration, reference_id)
+
+    def _init_relaxation(self, alpha, relaxation) -> None:
+        """``relaxation``, or ``alpha``, its deprecated name."""
+        if alpha is None:
+            self.relaxation = relaxation
+        else:
+            assert relaxation == 1, "You cannot specify relaxation and alpha simultaneously."
+            warnings.warn("alpha is deprecated. Set relaxation instead.", DeprecationWarning)
+            self.relaxation = alpha
+
     def _init_iterative(self, callbacks, record_loss) -> None:
         IterativeMethodBase.__init__(self, callbacks=callbacks, record_loss=record_loss)
         self.record_loss = record_loss  # (as given: None stays None, see the class docstring)
@@ -105,6 +132,14 @@ class ProxBSSBase(DemixingFilterBase):
             s += ", reference_id={reference_id}"
         s += ")"
         return s.format(**self.__dict__)
+
+    def _run(self, input, n_iter, initial_call, kwargs):
+        """``__call__`` of the splitting separators (ref: ssspy/bss/pdsbss.py:126-156, :320-350;
+        ssspy/bss/admmbss.py:121-151, :342-355)."""
+        self._bind_input(input)
+        self._reset(**kwargs)
+        IterativeMethodBase.__call__(self, n_iter=n_iter, initial_call=initial_call)
+        return self._finish_call()
 
     def _reset(self, **kwargs) -> None:
         """ref: ssspy/bss/proxbss.py:107-139."""
@@ -127,10 +162,53 @@ class ProxBSSBase(DemixingFilterBase):
             raise ValueError("demix_filter=None cannot be given at reset.")
         self._state_set_dev("output", _ops.separate(self._X, self._state_dev("demix_filter")))
 
+    def _penalty_state_shape(self):
+        """The shape of a spectrogram-sized state: an axis of penalties unless masking."""
+        B, N, F, T = self._X.shape
+        return (B, N, F, T) if self._masking else (B, self.n_penalties, N, F, T)
+
+    def _reset_states(self, shapes) -> None:
+        """The states ``{name: shape}`` beside the filters: zeros unless given by keyword, then copied
+        (ref: ssspy/bss/pdsbss.py:173-195, :366-389; ssspy/bss/admmbss.py:168-218, :357-408)."""
+        for name, shape in shapes.items():
+            if not self._state_has(name):
+                self._state_set_dev(name, dv.zeros(shape, dv.c128, self._X.device))
+            elif not self._state_is_none(name):
+                # (a copy: a state given by keyword is not overwritten)
+                setattr(self, name, np.array(getattr(self, name), dtype=np.complex128, copy=True))
+            if self._state_is_none(name):
+                raise ValueError("{}=None cannot be given at reset.".format(name))
+            got = tuple(self._state_dev(name).shape)
+            if got != shape:
+                skip = 0 if self._batched else 1
+                raise ValueError("{} must have shape {}, got {}.".format(name, shape[skip:],
+                                                                         got[skip:]))
+
+    def _state5(self, name):
+        """A spectrogram-sized state as (B, Q, N, F, T) (a view for the masking classes)."""
+        state = self._state_dev(name)
+        return state if state.dim() == 5 else state.unsqueeze(1)
+
+    def _host_prox(self, Z, prox_penalty, step_size, residual=False):
+        """The compatibility path: ``prox_penalty(Z)`` on the host, once per mixture of Z
+        (B, N, F, T); ``residual``: ``Z - prox_penalty(Z)``.  The shape is checked on what is
+        returned, so under ``residual`` the operator's value may broadcast against Z, as in the
+        reference (ssspy/bss/pdsbss.py:213)."""
+        V = [np.asarray(prox_penalty(Zb, step_size=step_size)) for Zb in Z]
+        V = np.stack([Zb - Vb for Zb, Vb in zip(Z, V)] if residual else V)
+        if V.shape != Z.shape:
+            raise ValueError("prox_penalty must map (n_sources, n_bins, n_frames) to the "
+                             "same shape.")
+        return V
+
+    def _host_mask_fn(self, Z):
+        """``mask_fn(Z)`` on the host, once per mixture, broadcast to Z (B, N, F, T)."""
+        return np.stack([np.broadcast_to(np.asarray(self.mask_fn(Zb)), Zb.shape) for Zb in Z])
+
     @property
     def n_penalties(self):
         """Number of penalty terms."""
-        return len(self.prox_penalty)
+        return 1 if self._masking else len(self.prox_penalty)
 
     def separate(self, input: np.ndarray, demix_filter: np.ndarray) -> np.ndarray:
         """y_ij = W_i x_ij (ref: ssspy/bss/proxbss.py:147-170); NumPy in, NumPy out."""
@@ -141,7 +219,17 @@ class ProxBSSBase(DemixingFilterBase):
         return Y if batched else Y[0]
 
     def _penalty_fns(self):
-        return self.penalty_fn
+        return [self.penalty_fn] if self._masking else self.penalty_fn
+
+    def _host_penalties(self, Y):
+        """sum_q penalty_q(Y) of every mixture of the device estimate Y, on the host."""
+        values = []
+        for Yb in dv.to_host(Y):
+            penalty = 0
+            for penalty_fn in self._penalty_fns():
+                penalty = penalty + penalty_fn(Yb)
+            values.append(penalty)
+        return values
 
     def compute_loss(self) -> float:
         """sum_q penalty_q(Y) - sum_i log|det W_i| (ref: ssspy/bss/proxbss.py:172-189): the penalties
@@ -150,13 +238,7 @@ class ProxBSSBase(DemixingFilterBase):
         logdet = _ops.sum_logdet(W)
         Y = _ops.separate(self._X, W)
         self._check_device_errors()
-        values = []
-        for Yb in dv.to_host(Y):
-            penalty = 0
-            for penalty_fn in self._penalty_fns():
-                penalty = penalty + penalty_fn(Yb)
-            values.append(penalty)
-        values = np.asarray(values, dtype=np.float64).reshape(-1)
+        values = np.asarray(self._host_penalties(Y), dtype=np.float64).reshape(-1)
         return self._loss_entry(values - dv.to_host(logdet))
 
     def compute_logdet(self, demix_filter: np.ndarray) -> np.ndarray:

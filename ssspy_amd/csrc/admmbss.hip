@@ -3,19 +3,18 @@
 //
 // The state is W (B,F,N,N), auxiliary1 / dual1 (B,F,N,N) and auxiliary2 / dual2 (B,Q,N,F,T).
 // Once per call:
-//   k_admm_contract (operand X) + k_admm_invert: Ainv_i = (Q conj(X_i) X_i^T + I)^-1, Hermitian positive
+//   k_prox_contract (operand X) + k_admm_invert: Ainv_i = (Q conj(X_i) X_i^T + I)^-1, Hermitian positive
 //   definite and constant over the iterations (the reference rebuilds and solves it every iteration)
 // An iteration is three passes:
-//   (a) k_admm_contract:    R_i = (sum_q (auxiliary2_q - dual2_q))_i X_i^H per bin
+//   (a) k_prox_contract:    R_i = (sum_q (auxiliary2_q - dual2_q))_i X_i^H per bin
 //   (b) k_admm_filter_step: W = Ainv (auxiliary1 - dual1 + R), U = relax W + (1 - relax) auxiliary1,
 //       auxiliary1 <- prox_{-log|det| / rho}(U + dual1), dual1 <- dual1 + U - auxiliary1; a lane per bin
 //   (c) k_admm_aux_step:    per penalty Z = relax W x + (1 - relax) auxiliary2_q + dual2_q,
 //       auxiliary2_q <- prox_q(Z, 1 / rho), dual2_q <- Z - auxiliary2_q
 // Z is never stored: the pass that needs it forms it again (k_admm_bin_norms for l21 over bins, the
-// first walk of l21 over frames).  fp64 / complex128, no atomics, every sum in a fixed order: two runs
-// give the same bits.
+// first walk of l21 over frames).  The contraction is that of prox_passes.hpp with this family's operand.
 #include "common.hpp"
-#include "pds_common.hpp"
+#include "prox_passes.hpp"
 #include "prox_svd.hpp"
 
 namespace ssspy {
@@ -23,78 +22,9 @@ namespace ssspy {
 namespace {
 
 constexpr int RM = SSSPY_RT_MAX_SOURCES;
-constexpr int ADMM_MAX_CHUNKS = FOLD_GROUP;  // (one level of k_fold_slabs: no scratch)
-// a `kind` of k_admm_aux_step past the public SSSPY_PROX_* ones: Z to zout, the state untouched
-constexpr int ADMM_KIND_FORM_Z = SSSPY_PROX_GIVEN + 1;
-
-// ---- R[b,i,n,m] = sum_j d[b,n,i,j] conj(X[b,m,i,j]) with d = sum_q (P_q - S_q), or d = P (Q = 1)
-// where S is NULL (the Gram matrix of the mixture with P = X).  grid (F, B), 256 threads; the thread
-// layout and the order of every sum are those of k_pds_contract (pdsbss.hip).
-template <int G>
-__global__ __launch_bounds__(PDS_THREADS) void k_admm_contract(const c128 *__restrict__ P,
-                                                               const c128 *__restrict__ S,
-                                                               const c128 *__restrict__ X, c128 *R,
-                                                               int Q, int N, int F, int T) {
-  constexpr int FL = PDS_THREADS / G;
-  constexpr int SW = FL < 64 ? FL : 64;       // frame lanes of a row inside one wave
-  constexpr int WPR = FL > 64 ? FL / 64 : 1;  // waves per row
-  __shared__ c128 Ps[G * WPR * G];
-  const int tid = threadIdx.x, n = tid / FL, jl = tid % FL;
-  const int i = blockIdx.x, b = blockIdx.y;
-  const bool src = n < N;
-  const long long FT = (long long)F * T;
-  const c128 *__restrict__ Xb = X + ((long long)b * N * F + i) * T;  // row m at Xb + m FT
-  const long long off = (long long)b * Q * N * FT + ((long long)(src ? n : 0) * F + i) * T;
-  c128 acc[G];
-#pragma unroll
-  for (int m = 0; m < G; ++m) acc[m] = cmake(0.0, 0.0);
-  if (src) {
-    for (int j = jl; j < T; j += FL) {
-      c128 d = P[off + j];
-      if (S) {
-        d = csub(d, S[off + j]);
-        for (int q = 1; q < Q; ++q) {
-          const long long e = off + (long long)q * N * FT + j;
-          d = cadd(d, csub(P[e], S[e]));
-        }
-      }
-#pragma unroll
-      for (int m = 0; m < G; ++m)
-        if (m < N) {
-          const c128 x = Xb[m * FT + j];
-          // acc += d conj(x)
-          acc[m].x = fma(d.x, x.x, acc[m].x);
-          acc[m].x = fma(d.y, x.y, acc[m].x);
-          acc[m].y = fma(d.y, x.x, acc[m].y);
-          acc[m].y = fma(-d.x, x.y, acc[m].y);
-        }
-    }
-  }
-#pragma unroll
-  for (int o = SW / 2; o > 0; o >>= 1) {
-#pragma unroll
-    for (int m = 0; m < G; ++m) {
-      acc[m].x += __shfl_xor(acc[m].x, o, 64);
-      acc[m].y += __shfl_xor(acc[m].y, o, 64);
-    }
-  }
-  if (jl % 64 == 0) {
-    const int w = jl / 64;
-#pragma unroll
-    for (int m = 0; m < G; ++m) Ps[(n * WPR + w) * G + m] = acc[m];
-  }
-  __syncthreads();
-  if (tid < N * N) {
-    const int r = tid / N, m = tid % N;
-    c128 s = Ps[(r * WPR) * G + m];
-#pragma unroll
-    for (int w = 1; w < WPR; ++w) s = cadd(s, Ps[(r * WPR + w) * G + m]);
-    R[(((long long)b * F + i) * N + r) * N + m] = s;
-  }
-}
 
 // ---- A = Q conj(Gm) + I -> A^-1 in place for n matrices, a lane per matrix on private memory, with
-// Gm[r][c] = sum_j x_r conj(x_c) from k_admm_contract: A = L L^H (Cholesky on the lower triangle),
+// Gm[r][c] = sum_j x_r conj(x_c) from k_prox_contract: A = L L^H (Cholesky on the lower triangle),
 // M = L^-1, A^-1 = M^H M.  NT as in k_prox_neg_logdet.  No votes: a lane past the end leaves.
 template <int NT>
 __global__ __launch_bounds__(64) void k_admm_invert(c128 *GA, long long n, int n_rt, double Qd) {
@@ -186,6 +116,23 @@ __global__ __launch_bounds__(64) void k_admm_filter_step(const c128 *__restrict_
     }
 }
 
+// the operand of the contraction: d = sum_q (P_q - S_q), the penalties added in order, or d = P
+// (Q = 1) where S is NULL (the Gram matrix of the mixture with P = X)
+struct AdmmOperand {
+  const c128 *__restrict__ P, *__restrict__ S;
+  __device__ __forceinline__ c128 at(long long off, int j, int Q, long long NFT) const {
+    c128 d = P[off + j];
+    if (S) {
+      d = csub(d, S[off + j]);
+      for (int q = 1; q < Q; ++q) {
+        const long long e = off + q * NFT + j;
+        d = cadd(d, csub(P[e], S[e]));
+      }
+    }
+    return d;
+  }
+};
+
 // z_n = relax (W x)_n + (1 - relax) a_n + d_n for the N rows of one (bin, frame); Wn: row-major N x N.
 // mix == false (relaxation 1): a is not read, z_n = (W x)_n + d_n.
 template <int G, typename WPtr>
@@ -216,11 +163,11 @@ __device__ __forceinline__ void admm_form_z(c128 (&z)[G], const c128 *__restrict
 // ---- the group norms of l21 over bins: part[c,b,n,j] = sum over the bins of chunk c of |Z|^2, in
 // bin order.  grid (ceil(T / 256), C, B); a thread owns one frame.  No barriers.
 template <int G>
-__global__ __launch_bounds__(PDS_THREADS) void k_admm_bin_norms(
+__global__ __launch_bounds__(PROX_THREADS) void k_admm_bin_norms(
     const c128 *__restrict__ X, const c128 *__restrict__ W, const c128 *__restrict__ aux2,
     const c128 *__restrict__ dual2, long long bstride, int N, int F, int T, int FC, double relax,
     double *part) {
-  const int j = blockIdx.x * PDS_THREADS + threadIdx.x;
+  const int j = blockIdx.x * PROX_THREADS + threadIdx.x;
   const int c = blockIdx.y, b = blockIdx.z, B = gridDim.z;
   if (j >= T) return;
   const long long FT = (long long)F * T;
@@ -243,27 +190,20 @@ __global__ __launch_bounds__(PDS_THREADS) void k_admm_bin_norms(
     if (n < N) part[(((long long)c * B + b) * N + n) * T + j] = r[n];
 }
 
-// max(1 - step / max(norm, step), 0): the factor of l1 / l21 (ref: ssspy/linalg/prox.py:6-33)
-__device__ __forceinline__ double admm_shrink(double norm, double step) {
-  norm = norm < step ? step : norm;
-  const double s = 1.0 - step / norm;
-  return s < 0.0 ? 0.0 : s;  // (NaN propagates, as through np.maximum)
-}
-
 // ---- (c) one penalty's auxiliary step.  grid (F, B), 256 threads; thread j walks frames j, j + 256,
 // ... with the N rows of Z in registers; a thread reads the N entries of auxiliary2_q / dual2_q of its
 // frame before it writes them.
 //   kind L1 / L21_SOURCES / L21_BINS (r2 (B,N,T) from k_admm_bin_norms) / L21_FRAMES (the norm of a
 //   row of the bin: a first walk and a block sum in wave order) / MASK (given (B,N,F,T): the mask,
-//   auxiliary2_q <- given Z) / GIVEN (given is prox(Z), formed on the host) / ADMM_KIND_FORM_Z (Z to
+//   auxiliary2_q <- given Z) / GIVEN (given is prox(Z), formed on the host) / PROX_KIND_FORM_Z (Z to
 //   zout, the state untouched).
 template <int G>
-__global__ __launch_bounds__(PDS_THREADS) void k_admm_aux_step(
+__global__ __launch_bounds__(PROX_THREADS) void k_admm_aux_step(
     const c128 *__restrict__ X, const c128 *__restrict__ W, c128 *aux2, c128 *dual2, long long bstride,
     int N, int F, int T, int kind, double step, double relax, const double *__restrict__ r2,
     const c128 *__restrict__ given, c128 *zout) {
   __shared__ c128 Ws[G * G];
-  __shared__ double Rs[PDS_THREADS / 64][G];
+  __shared__ double Rs[PROX_THREADS / 64][G];
   __shared__ double Rn[G];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int i = blockIdx.x, b = blockIdx.y;
@@ -279,7 +219,7 @@ __global__ __launch_bounds__(PDS_THREADS) void k_admm_aux_step(
     double r[G];
 #pragma unroll
     for (int n = 0; n < G; ++n) r[n] = 0.0;
-    for (int j = tid; j < T; j += PDS_THREADS) {
+    for (int j = tid; j < T; j += PROX_THREADS) {
       c128 z[G];
       admm_form_z<G>(z, Xb, Ab, Db, Ws, N, FT, j, relax, mix);
 #pragma unroll
@@ -294,15 +234,15 @@ __global__ __launch_bounds__(PDS_THREADS) void k_admm_aux_step(
     if (tid < G) {
       double s = Rs[0][tid];
 #pragma unroll
-      for (int w = 1; w < PDS_THREADS / 64; ++w) s += Rs[w][tid];
+      for (int w = 1; w < PROX_THREADS / 64; ++w) s += Rs[w][tid];
       Rn[tid] = s;
     }
     __syncthreads();
   }
-  for (int j = tid; j < T; j += PDS_THREADS) {
+  for (int j = tid; j < T; j += PROX_THREADS) {
     c128 z[G];
     admm_form_z<G>(z, Xb, Ab, Db, Ws, N, FT, j, relax, mix);
-    if (kind == ADMM_KIND_FORM_Z) {
+    if (kind == PROX_KIND_FORM_Z) {
 #pragma unroll
       for (int n = 0; n < G; ++n)
         if (n < N) zout[given_off + n * FT + j] = z[n];
@@ -327,7 +267,7 @@ __global__ __launch_bounds__(PDS_THREADS) void k_admm_aux_step(
           else if (kind == SSSPY_PROX_L21_SOURCES) norm2 = all2;
           else if (kind == SSSPY_PROX_L21_BINS) norm2 = r2[((long long)b * N + n) * T + j];
           else norm2 = Rn[n];
-          v = cscale(z[n], admm_shrink(sqrt(norm2), step));
+          v = cscale(z[n], prox_shrink(sqrt(norm2), step));
         }
         Ab[n * FT + j] = v;
         Db[n * FT + j] = csub(z[n], v);
@@ -336,42 +276,23 @@ __global__ __launch_bounds__(PDS_THREADS) void k_admm_aux_step(
   }
 }
 
-// bins per chunk and chunks of the l21-over-bins norm pass
-static void admm_chunks(int F, int &FC, int &C) {
-  const int want = F < ADMM_MAX_CHUNKS ? F : ADMM_MAX_CHUNKS;
-  FC = (F + want - 1) / want;
-  C = (F + FC - 1) / FC;
-}
-
 static int launch_contract(const c128 *P, const c128 *S, const c128 *X, c128 *R, int B, int Q, int N,
                            int F, int T, hipStream_t st) {
-  SSSPY_PDS_DISPATCH_G(N, hipLaunchKernelGGL((k_admm_contract<GG>), dim3((unsigned)F, (unsigned)B),
-                                             dim3(PDS_THREADS), 0, st, P, S, X, R, Q, N, F, T));
-  return check_launch("k_admm_contract");
+  const AdmmOperand op = {P, S};
+  SSSPY_PROX_DISPATCH_G(N, hipLaunchKernelGGL((k_prox_contract<GG, AdmmOperand>),
+                                              dim3((unsigned)F, (unsigned)B), dim3(PROX_THREADS), 0, st,
+                                              op, X, R, Q, N, F, T));
+  return check_launch("k_prox_contract");
 }
-
-// `CALL` with NN = the size at compile time (1..8) or 0 (9..16, the size at run time)
-#define SSSPY_ADMM_DISPATCH_N(N_, CALL)             \
-  switch (N_) {                                     \
-    case 1: { constexpr int NN = 1; CALL; } break;  \
-    case 2: { constexpr int NN = 2; CALL; } break;  \
-    case 3: { constexpr int NN = 3; CALL; } break;  \
-    case 4: { constexpr int NN = 4; CALL; } break;  \
-    case 5: { constexpr int NN = 5; CALL; } break;  \
-    case 6: { constexpr int NN = 6; CALL; } break;  \
-    case 7: { constexpr int NN = 7; CALL; } break;  \
-    case 8: { constexpr int NN = 8; CALL; } break;  \
-    default: { constexpr int NN = 0; CALL; } break; \
-  }
 
 static int launch_aux_step(const void *X, const void *W, void *aux2_q, void *dual2_q, long long bstride,
                            int kind, double step, double relax, const double *r2, const void *given,
                            void *zout, int B, int N, int F, int T, hipStream_t st) {
-  SSSPY_PDS_DISPATCH_G(N, hipLaunchKernelGGL((k_admm_aux_step<GG>), dim3((unsigned)F, (unsigned)B),
-                                             dim3(PDS_THREADS), 0, st, (const c128 *)X,
-                                             (const c128 *)W, (c128 *)aux2_q, (c128 *)dual2_q, bstride,
-                                             N, F, T, kind, step, relax, r2, (const c128 *)given,
-                                             (c128 *)zout));
+  SSSPY_PROX_DISPATCH_G(N, hipLaunchKernelGGL((k_admm_aux_step<GG>), dim3((unsigned)F, (unsigned)B),
+                                              dim3(PROX_THREADS), 0, st, (const c128 *)X,
+                                              (const c128 *)W, (c128 *)aux2_q, (c128 *)dual2_q, bstride,
+                                              N, F, T, kind, step, relax, r2, (const c128 *)given,
+                                              (c128 *)zout));
   return check_launch("k_admm_aux_step");
 }
 
@@ -385,26 +306,22 @@ extern "C" {
 
 int ssspy_admmbss_gram_inverse(const void *X, void *Ainv, int B, int Q, int N, int F, int T,
                                void *stream) {
-  SSSPY_REQUIRE(X && Ainv && Q > 0 && B > 0 && F > 0 && T > 0, "admmbss_gram_inverse: bad argument");
-  if (!pds_shape_ok(B, N, F, T))
-    return fail(SSSPY_ERR_UNSUPPORTED, "admmbss_gram_inverse: 1..16 sources, up to 65535 mixtures");
+  int rc = prox_check_args("admmbss_gram_inverse", X && Ainv && Q > 0, B, N, F, T);
+  if (rc != SSSPY_OK) return rc;
   hipStream_t st = as_stream(stream);
-  const int rc = launch_contract((const c128 *)X, nullptr, (const c128 *)X, (c128 *)Ainv, B, 1, N, F,
-                                 T, st);
+  rc = launch_contract((const c128 *)X, nullptr, (const c128 *)X, (c128 *)Ainv, B, 1, N, F, T, st);
   if (rc != SSSPY_OK) return rc;
   const long long n = (long long)B * F;
   const dim3 grid((unsigned)((n + 63) / 64)), block(64);
-  SSSPY_ADMM_DISPATCH_N(N, hipLaunchKernelGGL((k_admm_invert<NN>), grid, block, 0, st, (c128 *)Ainv, n,
-                                              N, (double)Q));
+  SSSPY_DISPATCH_N(N, hipLaunchKernelGGL((k_admm_invert<NN>), grid, block, 0, st, (c128 *)Ainv, n, N,
+                                         (double)Q));
   return check_launch("k_admm_invert");
 }
 
 int ssspy_admmbss_contract(const void *aux2, const void *dual2, const void *X, void *R, int B, int Q,
                            int N, int F, int T, void *stream) {
-  SSSPY_REQUIRE(aux2 && dual2 && X && R && Q > 0 && B > 0 && F > 0 && T > 0,
-                "admmbss_contract: bad argument");
-  if (!pds_shape_ok(B, N, F, T))
-    return fail(SSSPY_ERR_UNSUPPORTED, "admmbss_contract: 1..16 sources, up to 65535 mixtures");
+  const int rc = prox_check_args("admmbss_contract", aux2 && dual2 && X && R && Q > 0, B, N, F, T);
+  if (rc != SSSPY_OK) return rc;
   return launch_contract((const c128 *)aux2, (const c128 *)dual2, (const c128 *)X, (c128 *)R, B, Q, N,
                          F, T, as_stream(stream));
 }
@@ -418,39 +335,36 @@ int ssspy_admmbss_filter_step(const void *Ainv, const void *R, void *W, void *au
     return fail(SSSPY_ERR_UNSUPPORTED, "admmbss_filter_step: 1..16 sources");
   const long long n = (long long)B * F;
   const dim3 grid((unsigned)((n + 63) / 64)), block(64);
-  SSSPY_ADMM_DISPATCH_N(N, hipLaunchKernelGGL((k_admm_filter_step<NN>), grid, block, 0,
-                                              as_stream(stream), (const c128 *)Ainv, (const c128 *)R,
-                                              (c128 *)W, (c128 *)aux1, (c128 *)dual1, n, N, 1.0 / rho,
-                                              relaxation));
+  SSSPY_DISPATCH_N(N, hipLaunchKernelGGL((k_admm_filter_step<NN>), grid, block, 0, as_stream(stream),
+                                         (const c128 *)Ainv, (const c128 *)R, (c128 *)W, (c128 *)aux1,
+                                         (c128 *)dual1, n, N, 1.0 / rho, relaxation));
   return check_launch("k_admm_filter_step");
 }
 
 size_t ssspy_admmbss_bin_norms_workspace_bytes(int B, int N, int F, int T) {
-  if (!pds_shape_ok(B, N, F, T)) return 0;
+  if (!prox_shape_ok(B, N, F, T)) return 0;
   int FC, C;
-  admm_chunks(F, FC, C);
+  prox_chunks(F, FC, C);
   return (size_t)C * B * N * T * sizeof(double);
 }
 
 int ssspy_admmbss_bin_norms(const void *X, const void *W, const void *aux2_q, const void *dual2_q,
                             long long batch_stride, double relaxation, double *r2, int B, int N, int F,
                             int T, void *workspace, size_t workspace_bytes, void *stream) {
-  SSSPY_REQUIRE(X && W && aux2_q && dual2_q && r2 && workspace && B > 0 && F > 0 && T > 0,
-                "admmbss_bin_norms: bad argument");
-  if (!pds_shape_ok(B, N, F, T))
-    return fail(SSSPY_ERR_UNSUPPORTED, "admmbss_bin_norms: 1..16 sources, up to 65535 mixtures");
-  SSSPY_REQUIRE(batch_stride >= (long long)N * F * T, "admmbss_bin_norms: bad batch stride");
+  int rc = prox_check_args("admmbss_bin_norms", X && W && aux2_q && dual2_q && r2 && workspace, B, N, F,
+                           T, {"batch", batch_stride});
+  if (rc != SSSPY_OK) return rc;
   SSSPY_REQUIRE(workspace_bytes >= ssspy_admmbss_bin_norms_workspace_bytes(B, N, F, T),
                 "admmbss_bin_norms: workspace too small");
   int FC, C;
-  admm_chunks(F, FC, C);
+  prox_chunks(F, FC, C);
   hipStream_t st = as_stream(stream);
-  const dim3 grid((unsigned)((T + PDS_THREADS - 1) / PDS_THREADS), (unsigned)C, (unsigned)B);
-  SSSPY_PDS_DISPATCH_G(N, hipLaunchKernelGGL((k_admm_bin_norms<GG>), grid, dim3(PDS_THREADS), 0, st,
-                                             (const c128 *)X, (const c128 *)W, (const c128 *)aux2_q,
-                                             (const c128 *)dual2_q, batch_stride, N, F, T, FC,
-                                             relaxation, (double *)workspace));
-  const int rc = check_launch("k_admm_bin_norms");
+  const dim3 grid((unsigned)((T + PROX_THREADS - 1) / PROX_THREADS), (unsigned)C, (unsigned)B);
+  SSSPY_PROX_DISPATCH_G(N, hipLaunchKernelGGL((k_admm_bin_norms<GG>), grid, dim3(PROX_THREADS), 0, st,
+                                              (const c128 *)X, (const c128 *)W, (const c128 *)aux2_q,
+                                              (const c128 *)dual2_q, batch_stride, N, F, T, FC,
+                                              relaxation, (double *)workspace));
+  rc = check_launch("k_admm_bin_norms");
   if (rc != SSSPY_OK) return rc;
   return launch_fold_slabs((const double *)workspace, nullptr, r2, (long long)B * N * T, C, st);
 }
@@ -459,15 +373,9 @@ int ssspy_admmbss_aux_step(const void *X, const void *W, void *aux2_q, void *dua
                            long long batch_stride, int kind, double step_size, double relaxation,
                            const double *r2, const void *given, int B, int N, int F, int T,
                            void *stream) {
-  SSSPY_REQUIRE(X && W && aux2_q && dual2_q && aux2_q != dual2_q && B > 0 && F > 0 && T > 0,
-                "admmbss_aux_step: bad argument");
-  SSSPY_REQUIRE(kind >= SSSPY_PROX_L1 && kind <= SSSPY_PROX_GIVEN, "admmbss_aux_step: bad kind");
-  SSSPY_REQUIRE(kind != SSSPY_PROX_L21_BINS || r2, "admmbss_aux_step: l21 over bins needs r2");
-  SSSPY_REQUIRE((kind != SSSPY_PROX_MASK && kind != SSSPY_PROX_GIVEN) || given,
-                "admmbss_aux_step: this kind needs given");
-  if (!pds_shape_ok(B, N, F, T))
-    return fail(SSSPY_ERR_UNSUPPORTED, "admmbss_aux_step: 1..16 sources, up to 65535 mixtures");
-  SSSPY_REQUIRE(batch_stride >= (long long)N * F * T, "admmbss_aux_step: bad batch stride");
+  const int rc = prox_check_args("admmbss_aux_step", X && W && aux2_q && dual2_q && aux2_q != dual2_q,
+                                 B, N, F, T, {"batch", batch_stride}, {"given", kind, r2, given});
+  if (rc != SSSPY_OK) return rc;
   return launch_aux_step(X, W, aux2_q, dual2_q, batch_stride, kind, step_size, relaxation, r2, given,
                          nullptr, B, N, F, T, as_stream(stream));
 }
@@ -475,13 +383,11 @@ int ssspy_admmbss_aux_step(const void *X, const void *W, void *aux2_q, void *dua
 int ssspy_admmbss_form_z(const void *X, const void *W, const void *aux2_q, const void *dual2_q,
                          long long batch_stride, double relaxation, void *Z, int B, int N, int F,
                          int T, void *stream) {
-  SSSPY_REQUIRE(X && W && aux2_q && dual2_q && Z && Z != aux2_q && Z != dual2_q && B > 0 && F > 0 &&
-                    T > 0,
-                "admmbss_form_z: bad argument");
-  if (!pds_shape_ok(B, N, F, T))
-    return fail(SSSPY_ERR_UNSUPPORTED, "admmbss_form_z: 1..16 sources, up to 65535 mixtures");
-  SSSPY_REQUIRE(batch_stride >= (long long)N * F * T, "admmbss_form_z: bad batch stride");
-  return launch_aux_step(X, W, (void *)aux2_q, (void *)dual2_q, batch_stride, ADMM_KIND_FORM_Z, 0.0,
+  const int rc = prox_check_args(
+      "admmbss_form_z", X && W && aux2_q && dual2_q && Z && Z != aux2_q && Z != dual2_q, B, N, F, T,
+      {"batch", batch_stride});
+  if (rc != SSSPY_OK) return rc;
+  return launch_aux_step(X, W, (void *)aux2_q, (void *)dual2_q, batch_stride, PROX_KIND_FORM_Z, 0.0,
                          relaxation, nullptr, nullptr, Z, B, N, F, T, as_stream(stream));
 }
 

@@ -21,7 +21,7 @@
 // Both read one table cos(pi j / (F - 1)), j < 2 (F - 1) (k_hva_cos_table).
 // fp64, no atomics, every sum in a fixed order: two runs give the same bits.
 #include "common.hpp"
-#include "pds_common.hpp"
+#include "prox_passes.hpp"
 
 #include <cmath>
 
@@ -239,7 +239,7 @@ __global__ __launch_bounds__(HVA_THREADS) void k_hva_cepstrum(
 // ---- the masked dual step.  grid (F, B), 256 threads; thread j walks frames j, j + 256, ... with
 // the N rows of Z in registers, as k_pds_dual_step.
 template <int G>
-__global__ __launch_bounds__(PDS_THREADS) void k_hva_dual_step(
+__global__ __launch_bounds__(PROX_THREADS) void k_hva_dual_step(
     const c128 *__restrict__ X, const c128 *__restrict__ W2, c128 *dual, long long dual_bstride,
     const double *__restrict__ varrho, int N, int F, int T, double gamma, double relax) {
   __shared__ c128 Ws[G * G];
@@ -251,7 +251,7 @@ __global__ __launch_bounds__(PDS_THREADS) void k_hva_dual_step(
   const double *__restrict__ Vb = varrho + ((long long)b * N * F + i) * T;  // row n at + n FT
   if (tid < N * N) Ws[tid] = W2[((long long)b * F + i) * (N * N) + tid];
   __syncthreads();
-  for (int j = tid; j < T; j += PDS_THREADS) {
+  for (int j = tid; j < T; j += PROX_THREADS) {
     c128 z[G];
     pds_form_z<G>(z, Xb, Db, Ws, N, FT, j);
     double vr[G];
@@ -308,7 +308,7 @@ int ssspy_hva_cepstrum(const void *X, const void *W2, const void *dual_q,
                 "hva_cepstrum: bad argument");
   SSSPY_REQUIRE(floor_kind >= SSSPY_FLOOR_NONE && floor_kind <= SSSPY_FLOOR_ADD,
                 "hva_cepstrum: bad flooring");
-  if (!pds_shape_ok(B, N, F, T))
+  if (!prox_shape_ok(B, N, F, T))
     return fail(SSSPY_ERR_UNSUPPORTED, "hva_cepstrum: 1..16 sources, up to 65535 mixtures");
   SSSPY_REQUIRE(dual_batch_stride >= (long long)N * F * T, "hva_cepstrum: bad dual stride");
   const HvaPlan plan = hva_plan(F, route);
@@ -339,14 +339,13 @@ int ssspy_hva_cepstrum(const void *X, const void *W2, const void *dual_q,
 int ssspy_hva_dual_step(const void *X, const void *W2, void *dual_q, long long dual_batch_stride,
                         const double *varrho, double attenuation, double relaxation, int B, int N,
                         int F, int T, void *stream) {
-  SSSPY_REQUIRE(X && W2 && dual_q && varrho && B > 0 && F > 0 && T > 0, "hva_dual_step: bad argument");
-  if (!pds_shape_ok(B, N, F, T))
-    return fail(SSSPY_ERR_UNSUPPORTED, "hva_dual_step: 1..16 sources, up to 65535 mixtures");
-  SSSPY_REQUIRE(dual_batch_stride >= (long long)N * F * T, "hva_dual_step: bad dual stride");
-  SSSPY_PDS_DISPATCH_G(N, hipLaunchKernelGGL((k_hva_dual_step<GG>), dim3((unsigned)F, (unsigned)B),
-                                             dim3(PDS_THREADS), 0, as_stream(stream), (const c128 *)X,
-                                             (const c128 *)W2, (c128 *)dual_q, dual_batch_stride,
-                                             varrho, N, F, T, attenuation, relaxation));
+  const int rc = prox_check_args("hva_dual_step", X && W2 && dual_q && varrho, B, N, F, T,
+                                 {"dual", dual_batch_stride});
+  if (rc != SSSPY_OK) return rc;
+  SSSPY_PROX_DISPATCH_G(N, hipLaunchKernelGGL((k_hva_dual_step<GG>), dim3((unsigned)F, (unsigned)B),
+                                              dim3(PROX_THREADS), 0, as_stream(stream), (const c128 *)X,
+                                              (const c128 *)W2, (c128 *)dual_q, dual_batch_stride,
+                                              varrho, N, F, T, attenuation, relaxation));
   return check_launch("k_hva_dual_step");
 }
 

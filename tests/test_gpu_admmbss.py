@@ -252,6 +252,24 @@ def test_mask_and_given_passes(relax):
         assert rel_err(_host(dd)[:, 0], Z - want) < OP_TOL
 
 
+@pytest.mark.parametrize("shape", [(2, 3, 5, 70), (1, 16, 2, 7), (1, 2, 1, 257)], **_ids)
+def test_z_at_relaxation_one_is_the_pds_z(shape):
+    """The Z formers of the two families are kept in step by hand: at relaxation 1 the ADMM Z and its
+    norms over bins are those of PDSBSS bit for bit, and auxiliary2 (NaN here) is not read."""
+    from ssspy_amd import _ops
+
+    B, N, F, T = shape
+    rng = np.random.default_rng(53)
+    dX, dW = _dev(_crandn(rng, B, N, F, T)), _dev(_crandn(rng, B, F, N, N) / np.sqrt(N))
+    dd = _dev(_crandn(rng, B, 1, N, F, T))
+    da = _dev(np.full((B, 1, N, F, T), np.nan + 1j * np.nan))
+    Z = _host(_ops.pdsbss_form_z(dX, dW, dd, 0))
+    assert np.isfinite(Z).all()
+    assert np.array_equal(_host(_ops.admmbss_form_z(dX, dW, da, dd, 0, 1.0)), Z)
+    assert np.array_equal(_host(_ops.admmbss_bin_norms(dX, dW, da, dd, 0, 1.0)),
+                          _host(_ops.pdsbss_bin_norms(dX, dW, dd, 0)))
+
+
 # ------------------------------------------------------------------ the classes
 def _construct(ns, prox_ns, spec, **extra):
     with warnings.catch_warnings():

@@ -430,6 +430,32 @@ def test_device_operator_equals_anonymous_closure(kind):
     assert max(errs) < OP_TOL
 
 
+@pytest.mark.parametrize("value", ["scalar", "row"])
+def test_host_operator_may_broadcast_against_z(value):
+    """The compatibility path forms ``Z - prox_penalty(Z)`` as the reference does
+    (ssspy/bss/pdsbss.py:213), so an operator may return what merely broadcasts against Z: a scalar,
+    or one value per (source, frame).  The same bits as with the value written out in Z's shape."""
+
+    def short(z, step_size=1):
+        if value == "scalar":
+            return 0.25 * step_size
+        return np.mean(z, axis=1, keepdims=True) / (1 + step_size)
+
+    def full(z, step_size=1):
+        return np.broadcast_to(short(z, step_size=step_size), z.shape).astype(z.dtype)
+
+    spec = dict(pc.DEFAULTS, N=3, F=5, T=70, seed=2, penalties=["l1"])  # (one penalty: the scale of X)
+    X = _batch(spec, B=2)
+    runs = []
+    for fn in (short, full):
+        m = _pds().PDSBSS(prox_penalty=fn, relaxation=1.25)
+        Y = m(X, n_iter=3)
+        runs.append((Y, np.array(m.demix_filter), np.array(m.dual)))
+    assert runs[0][2].shape == (2, 1, 3, 5, 70)
+    for a, b in zip(*runs):
+        assert np.array_equal(np.asarray(a), np.asarray(b))
+
+
 def test_update_once_by_hand_equals_call():
     spec = dict(pc.DEFAULTS, N=3, F=9, T=70, seed=2, penalties=["l21_bins", "l1"],
                 scale_restoration=False)
