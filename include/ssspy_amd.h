@@ -1391,6 +1391,72 @@ int ssspy_ipsdta_vcd(void *W, const void *weighted_covariance, int B, int F, int
 int ssspy_matmul3(const void *A, const void *Bm, const void *C, void *out, long long n, int L,
                   void *stream);
 
+/* ------------------------------------------------------------------ permutation alignment
+ * The two solvers of ssspy/algorithm/permutation_alignment.py, batched and device-resident
+ * (csrc/permutation.hip), with the decisions of the host solvers of this package: the first
+ * permutation, in itertools.permutations(range(N)) order, of the largest score.
+ * A sequence is addressed by strides in elements: (b, n, f, t) at
+ * b * stride_b + n * stride_n + f * stride_f + t.  perm is int32 (B, F, N): aligned component n of
+ * bin f is original component perm[b, f, n].  2..8 sources (N! permutations are enumerated per
+ * bin).  Every sum runs in a fixed order; two runs give the same bits.
+ * (Added at SSSPY_ABI_VERSION 11 without a bump: no existing argument list changed.) */
+enum { SSSPY_PERM_SOLVER_CORRELATION = 0, SSSPY_PERM_SOLVER_SCORE = 1 };
+enum { SSSPY_PERM_ROUTE_DEVICE = 0, SSSPY_PERM_ROUTE_HOST = 1 };
+/* layouts of ssspy_permute_sources */
+enum {
+  SSSPY_PERM_LAYOUT_BIN_SOURCE = 0, /* (B, F, N, inner): filters, the host order of the solvers */
+  SSSPY_PERM_LAYOUT_SOURCE_BIN = 1, /* (B, N, F, inner): spectrograms, posteriors, mixing weights  */
+};
+
+/* SSSPY_PERM_ROUTE_DEVICE where the kernels below take N sources and T frames with `solver` and the
+ * floor `floor_kind` (SSSPY_FLOOR_*; anything else stands for a callable only the host can run),
+ * SSSPY_PERM_ROUTE_HOST otherwise: fewer than 2 or more than 8 sources, an unknown floor, or, for
+ * the correlation solver, N * T > 16384 (its criterion stays in LDS).  -1 for a bad argument. */
+int ssspy_permutation_route(int N, int T, int solver, int floor_kind);
+
+/* index[m] = the first permutation p maximising sum_i tables[m, p[i], i]; tables (n_tables, N, N) */
+int ssspy_best_permutation(const double *tables, int *index, long long n_tables, int N,
+                           void *stream);
+
+/* envelope (B, F, N, T) = |y| / floor(sqrt(sum_n |y|^2)) and overlap (B, F) = the sum of all
+ * entries of P P^T per bin; sequence f64 (is_complex == 0) or c128. */
+int ssspy_permutation_envelope_overlap(const void *sequence, int is_complex, long long stride_b,
+                                       long long stride_n, long long stride_f, double *envelope,
+                                       double *overlap, int B, int N, int F, int T, int floor_kind,
+                                       double floor_eps, void *stream);
+
+/* The sweep of the correlation solver over the bins in `order` (B, F) int32 (the argsort of the
+ * overlaps): one workgroup per mixture, the criterion in LDS (N * T <= 16384). */
+int ssspy_permutation_correlation_sweep(const double *envelope, const int *order, int *perm, int B,
+                                        int N, int F, int T, void *stream);
+
+/* normalized (B, F, N, T): every (bin, component) at zero mean and unit population deviation */
+int ssspy_permutation_score_normalize(const double *sequence, long long stride_b, long long stride_n,
+                                      long long stride_f, double *normalized, int B, int N, int F,
+                                      int T, void *stream);
+
+/* global_iter rounds of the global stage on perm (B, F, N) in place (rows are addressed through it);
+ * centroid (B, N, T) is scratch, centroid_std (B, N) receives the deviation of the last centroid
+ * (with global_iter == 0 that of the sequences as perm orders them). */
+int ssspy_permutation_score_global(const double *normalized, int *perm, double *centroid,
+                                   double *centroid_std, int B, int N, int F, int T, int global_iter,
+                                   int floor_kind, double floor_eps, void *stream);
+
+/* local_iter walks over the bins in increasing order, one workgroup per mixture, on perm in place */
+int ssspy_permutation_score_local(const double *normalized, const double *centroid_std, int *perm,
+                                  int B, int N, int F, int T, int local_iter, int floor_kind,
+                                  double floor_eps, void *stream);
+
+/* dst = the sources of src gathered by perm, out of place, in 8-byte words: dst contiguous in
+ * `layout`, word w of (b, f, n) of src at b * stride_b + f * stride_f + n * stride_n + w. */
+int ssspy_permute_sources(const void *src, void *dst, const int *perm, int B, int N, int F,
+                          long long inner_words, int layout, long long stride_b, long long stride_f,
+                          long long stride_n, void *stream);
+
+/* out (B, N, F, T) = |posterior X[:, reference_id]|: the amplitude targets of CACGMM's alignment */
+int ssspy_permutation_amplitude(const double *posterior, const void *X, double *out, int B, int N,
+                                int M, int F, int T, int reference_id, void *stream);
+
 /* ------------------------------------------------------------------ STFT / ISTFT
  * The transforms the reference's workflow takes from SciPy either side of a separator
  * (tests/package/bss/test_ilrma.py, test_iva.py, test_mnmf.py: scipy.signal.stft(x, window="hann",

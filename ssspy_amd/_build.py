@@ -54,6 +54,7 @@ def _units():
         ("admmbss.hip", "admmbss.o", []),
         ("ipsdta.hip", "ipsdta.o", []),
         ("cacgmm.hip", "cacgmm.o", []),
+        ("permutation.hip", "permutation.o", []),
         ("iss_fused.hip", "iss_fused.o", []),
         ("linalg_kernels.hip", "linalg_kernels.o", []),
         ("pairwise_kernels.hip", "pairwise_kernels.o", []),

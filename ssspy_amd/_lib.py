@@ -55,6 +55,11 @@ PROX_L1, PROX_L21_SOURCES, PROX_L21_BINS, PROX_L21_FRAMES, PROX_MASK, PROX_GIVEN
 # SSSPY_HVA_ROUTE_*: `route` of the HVA entry points and what ssspy_hva_route returns
 HVA_ROUTE_AUTO, HVA_ROUTE_FFT, HVA_ROUTE_DIRECT = range(3)
 MAX_PAIRS = 32
+# SSSPY_PERM_*: `solver` of ssspy_permutation_route and what it returns; `layout` of
+# ssspy_permute_sources
+PERM_SOLVER_CORRELATION, PERM_SOLVER_SCORE = range(2)
+PERM_ROUTE_DEVICE, PERM_ROUTE_HOST = range(2)
+PERM_LAYOUT_BIN_SOURCE, PERM_LAYOUT_SOURCE_BIN = range(2)
 # SSSPY_MAX_SOURCES (per-N kernels: IPA, both MNMF classes, the Hermitian operators; GaussMNMF's
 # channels and the ILRMA partition entry points stop there), SSSPY_RT_MAX_SOURCES (run-time-N kernels:
 # the shared operators, ILRMA, AuxIVA, FastGaussMNMF's channels and sources, GaussMNMF's sources),
@@ -194,6 +199,16 @@ PROTOTYPES = {
     "ssspy_cacgmm_normalize": (_i, [_p, _i, _i, _i, _i, _p]),
     "ssspy_cacgmm_fold_loss": (_i, [_p, _p, _q, _i, _p]),
     "ssspy_cacgmm_separate": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "ssspy_permutation_route": (_i, [_i, _i, _i, _i]),
+    "ssspy_best_permutation": (_i, [_p, _p, _q, _i, _p]),
+    "ssspy_permutation_envelope_overlap": (_i, [_p, _i, _q, _q, _q, _p, _p, _i, _i, _i, _i, _i, _d,
+                                                _p]),
+    "ssspy_permutation_correlation_sweep": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
+    "ssspy_permutation_score_normalize": (_i, [_p, _q, _q, _q, _p, _i, _i, _i, _i, _p]),
+    "ssspy_permutation_score_global": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _d, _p]),
+    "ssspy_permutation_score_local": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _d, _p]),
+    "ssspy_permute_sources": (_i, [_p, _p, _p, _i, _i, _i, _q, _i, _q, _q, _q, _p]),
+    "ssspy_permutation_amplitude": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "ssspy_gmnmf_workspace_bytes": (_z, [_i, _i, _i, _i, _i, _i]),
     "ssspy_gmnmf_route": (_i, [_i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]),
     "ssspy_gmnmf_update": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _d, _p, _z, _p]),

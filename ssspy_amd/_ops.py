@@ -1420,6 +1420,140 @@ def cacgmm_separate(posterior, X, reference_id, out=None):
     return out
 
 
+# ---- permutation alignment (csrc/permutation.hip).  A sequence is a tensor indexed (b, n, f, t) with
+# the frames contiguous and any strides on the other axes -- the library's (B, N, F, T), or a
+# permuted view of the solvers' (B, F, N, T): nothing is copied.  perm is int32 (B, F, N).
+def permutation_route(N, T, solver, flooring):
+    """True where the device solver takes N sources and T frames with this floor.  Host only."""
+    kind = -1 if getattr(flooring, "host", None) is not None else int(flooring[0])
+    route = int(_L().ssspy_permutation_route(int(N), int(T), int(solver), kind))
+    if route < 0:
+        raise ValueError("permutation_route: bad argument")
+    return route == _lib.PERM_ROUTE_DEVICE
+
+
+def permutation_limit(N, T, solver, flooring):
+    """Why ``permutation_route`` says host, in words."""
+    if getattr(flooring, "host", None) is not None:
+        return "flooring_fn must be None, identity, max_flooring or add_flooring, got {!r}".format(
+            flooring.host)
+    if N < 2 or N > _lib.MAX_SOURCES:
+        return "2..{} sources, got {}".format(_lib.MAX_SOURCES, N)
+    return "n_sources * n_frames <= 16384 for the correlation solver, got {} x {}".format(N, T)
+
+
+def _sequence_strides(sequence, dtype_ok):
+    assert sequence.ndim == 4 and sequence.dtype in dtype_ok, "bad sequence"
+    if sequence.stride(3) != 1 and sequence.shape[3] > 1:
+        raise ValueError("the frames of a sequence must be contiguous")
+    return sequence.stride(0), sequence.stride(1), sequence.stride(2)
+
+
+def best_permutation(tables):
+    """Index, in ``itertools.permutations`` order, of the first permutation p maximising
+    sum_i tables[m, p[i], i]; tables (n, N, N) f64 -> int32 (n,)."""
+    n, N, _ = tables.shape
+    out = dv.empty((n,), dv.i32, tables.device)
+    _lib.check(_L().ssspy_best_permutation(ptr(tables), ptr(out), n, N, _st()), "best_permutation")
+    return out
+
+
+def permutation_envelope_overlap(sequence, flooring):
+    """(envelope (B, F, N, T), overlap (B, F)) of a real or complex sequence (b, n, f, t)."""
+    sb, sn, sf = _sequence_strides(sequence, (dv.f64, dv.c128))
+    B, N, F, T = sequence.shape
+    envelope = dv.empty((B, F, N, T), dv.f64, sequence.device)
+    overlap = dv.empty((B, F), dv.f64, sequence.device)
+    _lib.check(_L().ssspy_permutation_envelope_overlap(
+        sequence.data_ptr(), int(sequence.is_complex()), sb, sn, sf, ptr(envelope), ptr(overlap), B,
+        N, F, T, int(flooring[0]), float(flooring[1]), _st()), "permutation_envelope_overlap")
+    return envelope, overlap
+
+
+def permutation_correlation_sweep(envelope, order):
+    """perm (B, F, N) of the correlation solver; order (B, F) int32: the bins as they are visited."""
+    B, F, N, T = envelope.shape
+    assert tuple(order.shape) == (B, F) and order.dtype == dv.i32
+    perm = dv.empty((B, F, N), dv.i32, envelope.device)
+    _lib.check(_L().ssspy_permutation_correlation_sweep(ptr(envelope), ptr(order), ptr(perm), B, N, F,
+                                                        T, _st()), "permutation_correlation_sweep")
+    return perm
+
+
+def permutation_score_normalize(sequence):
+    """normalized (B, F, N, T) of a real sequence (b, n, f, t)."""
+    sb, sn, sf = _sequence_strides(sequence, (dv.f64,))
+    B, N, F, T = sequence.shape
+    normalized = dv.empty((B, F, N, T), dv.f64, sequence.device)
+    _lib.check(_L().ssspy_permutation_score_normalize(sequence.data_ptr(), sb, sn, sf,
+                                                      ptr(normalized), B, N, F, T, _st()),
+               "permutation_score_normalize")
+    return normalized
+
+
+def permutation_identity(B, F, N, dev):
+    """perm (B, F, N) of the sequences as they are (plumbing: a torch fill)."""
+    import torch
+
+    return torch.arange(N, dtype=dv.i32, device=dev).expand(B, F, N).contiguous()
+
+
+def permutation_score_global(normalized, perm, global_iter, flooring):
+    """The global stage on ``perm`` in place; returns centroid_std (B, N) of the last centroid."""
+    B, F, N, T = normalized.shape
+    assert tuple(perm.shape) == (B, F, N) and perm.dtype == dv.i32
+    centroid = dv.empty((B, N, T), dv.f64, normalized.device)
+    centroid_std = dv.empty((B, N), dv.f64, normalized.device)
+    _lib.check(_L().ssspy_permutation_score_global(
+        ptr(normalized), ptr(perm), ptr(centroid), ptr(centroid_std), B, N, F, T, int(global_iter),
+        int(flooring[0]), float(flooring[1]), _st()), "permutation_score_global")
+    return centroid_std
+
+
+def permutation_score_local(normalized, centroid_std, perm, local_iter, flooring):
+    """The local stage on ``perm`` in place."""
+    B, F, N, T = normalized.shape
+    assert tuple(perm.shape) == (B, F, N) and tuple(centroid_std.shape) == (B, N)
+    _lib.check(_L().ssspy_permutation_score_local(
+        ptr(normalized), ptr(centroid_std), ptr(perm), B, N, F, T, int(local_iter), int(flooring[0]),
+        float(flooring[1]), _st()), "permutation_score_local")
+    return perm
+
+
+def permute_sources(array, perm, layout):
+    """The sources of ``array`` gathered by ``perm`` into a new contiguous tensor of the same shape.
+    layout PERM_LAYOUT_BIN_SOURCE: array (B, F, N, ...), PERM_LAYOUT_SOURCE_BIN: (B, N, F, ...); the
+    leading three axes may be strided, the rest is contiguous; elements of 8 or 16 bytes."""
+    B, F, N = perm.shape
+    lead = (B, F, N) if layout == _lib.PERM_LAYOUT_BIN_SOURCE else (B, N, F)
+    assert tuple(array.shape[:3]) == lead and perm.dtype == dv.i32
+    words = array.element_size() // 8
+    if words * 8 != array.element_size():
+        raise NotImplementedError("permute_sources moves elements of 8 or 16 bytes, got {}".format(
+            array.dtype))
+    flat = array.reshape(lead + (-1,)) if array.ndim != 4 else array
+    if flat.shape[3] > 1 and flat.stride(3) != 1:
+        flat = flat.contiguous()
+    inner = flat.shape[3] * words
+    sb, s1, s2 = (flat.stride(k) * words for k in range(3))
+    sf, sn = (s1, s2) if layout == _lib.PERM_LAYOUT_BIN_SOURCE else (s2, s1)
+    out = dv.empty(tuple(array.shape), array.dtype, array.device)
+    if out.numel():
+        _lib.check(_L().ssspy_permute_sources(flat.data_ptr(), ptr(out), ptr(perm), B, N, F, inner,
+                                              int(layout), sb, sf, sn, _st()), "permute_sources")
+    return out
+
+
+def permutation_amplitude(posterior, X, reference_id):
+    """|posterior * X[:, reference_id]| (B, N, F, T)."""
+    B, N, F, T = posterior.shape
+    M = X.shape[1]
+    out = dv.empty((B, N, F, T), dv.f64, X.device)
+    _lib.check(_L().ssspy_permutation_amplitude(ptr(posterior), ptr(X), ptr(out), B, N, M, F, T,
+                                                int(reference_id), _st()), "permutation_amplitude")
+    return out
+
+
 # ---- IPSDTA (csrc/ipsdta.hip).  A partition is (basis (B, N, K, Cn, L, L), first bin, first block):
 # the blocks of one size, see ssspy_ipsdta_frame_pass.
 def ipsdta_frame_pass(X, W, part, activation, pi, n_blocks, mode, out0, out1=None, route=None):

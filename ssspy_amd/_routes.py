@@ -31,6 +31,10 @@ _DEFAULTS = {
     # as themselves) inside the statistics pass; False: the compatibility route every other callable
     # takes (Y down, Phi up once per iteration; bss.ica.route decides, once per call)
     "ica_named": True,
+    # FDICA and CACGMM align the permutations on the device (csrc/permutation.hip) where
+    # ssspy_permutation_route allows; False: the NumPy solvers on host copies, one mixture after the
+    # other (what 1 or 9..16 sources, flooring callables and overlong frame axes run)
+    "device_alignment": True,
 }
 VALUES = dict(_DEFAULTS)  # (tests: monkeypatch.setitem(_routes.VALUES, "implied_filter", False))
 

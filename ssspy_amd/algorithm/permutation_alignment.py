@@ -1,4 +1,6 @@
-"""Permutation alignment between frequency bins, on the host (NumPy).
+"""Permutation alignment between frequency bins: NumPy arrays on the host, torch device tensors on
+the device (csrc/permutation.hip; ``device_correlation_permutation`` / ``device_score_permutation``
+are what the separators call), with the same permutations.
 
 Counterparts of ``ssspy.algorithm.permutation_alignment``: the correlation-based solver of Murata,
 Ikeda and Ziehe (Neurocomputing 41, 2001) and the score-based solver of Sawada, Araki and Makino
@@ -19,6 +21,7 @@ from ..special.flooring import identity, max_flooring
 __all__ = ["correlation_based_permutation_solver", "score_based_permutation_solver"]
 
 EPS = 1e-10
+_CORRELATION, _SCORE = 0, 1  # _lib.PERM_SOLVER_* (this module loads no library for NumPy input)
 
 
 def _prepare(sequence, args, overwrite):
@@ -66,6 +69,77 @@ def _take_sources(array, order):
     return np.take_along_axis(array, index, axis=1)
 
 
+# -- the device solvers (csrc/permutation.hip) ----------------------------------------------------
+def _is_device_tensor(x):
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+def device_correlation_permutation(sequence, floor):
+    """perm int32 (B, F, N) of the correlation solver for a device sequence indexed (b, n, f, t),
+    real or complex; ``floor`` a resolved ``device_flooring``.  Only the (B, F) overlaps come to
+    the host, where ``numpy.argsort`` -- the call of the host solver -- orders the bins."""
+    from .. import _device as dv
+    from .. import _ops
+
+    envelope, overlap = _ops.permutation_envelope_overlap(sequence, floor)
+    order = np.stack([np.argsort(row) for row in dv.to_host(overlap)])
+    order = dv.to_device(order, dtype=np.int32, dev=sequence.device)
+    return _ops.permutation_correlation_sweep(envelope, order)
+
+
+def device_score_permutation(sequence, floor, global_iter=1, local_iter=1):
+    """perm int32 (B, F, N) of the score solver for a real device sequence indexed (b, n, f, t)."""
+    from .. import _ops
+
+    B, N, F, _ = sequence.shape
+    normalized = _ops.permutation_score_normalize(sequence)
+    perm = _ops.permutation_identity(B, F, N, sequence.device)
+    centroid_std = _ops.permutation_score_global(normalized, perm, global_iter, floor)
+    return _ops.permutation_score_local(normalized, centroid_std, perm, local_iter, floor)
+
+
+def _solve_on_device(solver, sequence, args, flooring_fn, overwrite, **iters):
+    """The public solvers on torch device tensors (n_bins, n_sources, n_frames) or batched
+    (n_mixtures, n_bins, n_sources, n_frames): wholly on the device, or ``NotImplementedError``."""
+    from .. import _lib, _ops
+    from ..utils.flooring import device_flooring
+
+    assert sequence.ndim in (3, 4), "Dimension of sequence is expected to be 3 (4 with a batch)."
+    lead = sequence.ndim - 1
+    for pos_idx, arg in enumerate(args):
+        if not _is_device_tensor(arg) or tuple(arg.shape[:lead]) != tuple(sequence.shape[:lead]):
+            raise ValueError("The shape of {}th argument is invalid.".format(pos_idx + 1))
+    if not sequence.is_cuda:
+        raise NotImplementedError("permutation alignment of a tensor runs on a HIP device only")
+
+    batched = sequence.ndim == 4
+    seq = sequence if batched else sequence[None]
+    others = [arg if batched else arg[None] for arg in args]
+    B, F, N, T = seq.shape
+    floor = device_flooring(flooring_fn, allow_host=True)
+    if not _ops.permutation_route(N, T, solver, floor):
+        raise NotImplementedError(
+            "permutation alignment on the device is limited to {} (convert to NumPy for the host "
+            "solver)".format(_ops.permutation_limit(N, T, solver, floor)))
+
+    view = seq.permute(0, 2, 1, 3)  # (b, n, f, t) through strides
+    if T > 1 and view.stride(3) != 1:
+        view = seq.contiguous().permute(0, 2, 1, 3)
+    if solver == _CORRELATION:
+        perm = device_correlation_permutation(view, floor)
+    else:
+        perm = device_score_permutation(view, floor, **iters)
+
+    results = [_ops.permute_sources(a, perm, _lib.PERM_LAYOUT_BIN_SOURCE) for a in [seq] + others]
+    if overwrite:
+        for given, result in zip([seq] + others, results):
+            given.copy_(result)
+        results = [seq] + others
+    if not batched:
+        results = [r[0] for r in results]
+    return _result(results[0], tuple(results[1:]))
+
+
 def correlation_based_permutation_solver(
     sequence: np.ndarray,
     *args,
@@ -80,6 +154,11 @@ def correlation_based_permutation_solver(
     they overlap most; each is permuted to correlate best with the sum of the envelopes aligned so
     far (the first bin keeps its order).
 
+    NumPy arrays are aligned on the host.  Torch device tensors -- (n_bins, n_sources, n_frames)
+    or a batch (n_mixtures, n_bins, n_sources, n_frames), ``args`` likewise -- are aligned on the
+    device and tensors come back; beyond the device limits (2..8 sources, the built-in floors,
+    n_sources * n_frames <= 16384) that raises ``NotImplementedError``.
+
     Args:
         sequence: (n_bins, n_sources, n_frames), real or complex.
         args: further arrays (n_bins, n_sources, ...) that receive the same permutations.
@@ -90,6 +169,9 @@ def correlation_based_permutation_solver(
         The permuted sequence; with one extra argument ``(sequence, arg)``, with more
         ``(sequence, (arg, ...))``.
     """
+    if _is_device_tensor(sequence):
+        return _solve_on_device(_CORRELATION, sequence, args, flooring_fn, overwrite)
+
     Y, permutable = _prepare(sequence, args, overwrite)
     if flooring_fn is None:
         flooring_fn = identity
@@ -154,10 +236,21 @@ def score_based_permutation_solver(
         multi_centroids: not supported.
         overwrite: permute ``args`` in place (and ``sequence`` where the reference does).
 
+    NumPy arrays are aligned on the host.  Torch device tensors -- (n_bins, n_sources, n_frames)
+    or a batch (n_mixtures, n_bins, n_sources, n_frames), ``args`` likewise -- are aligned on the
+    device and tensors come back (with ``overwrite`` the given tensors, the sequence included);
+    beyond the device limits (2..8 sources, the built-in floors) that raises
+    ``NotImplementedError``.
+
     Returns:
         The permuted sequence; with one extra argument ``(sequence, arg)``, with more
         ``(sequence, (arg, ...))``.
     """
+    if _is_device_tensor(sequence):
+        assert not multi_centroids, "multi_centroids version is not supported."
+        return _solve_on_device(_SCORE, sequence, args, flooring_fn, overwrite,
+                                global_iter=global_iter, local_iter=local_iter)
+
     assert sequence.ndim == 3, "Dimension of sequence is expected to be 3."
     assert not multi_centroids, "multi_centroids version is not supported."
 

@@ -5,8 +5,9 @@ on the direction vectors z = x / ||x||.  The E and the M step evaluate the quadr
 z^H B^-1 z with the same B, so one iteration is one pass over the unit mixture
 (``_ops.cacgmm_frame_pass``: the sums of the posteriors, the weighted outer products and the loss of
 the parameters it was given) and one per-(source, bin) step (``_ops.cacgmm_parameter_step``).  The
-posterior is formed only when somebody reads it; permutation alignment runs on the host, once per
-call (``ssspy_amd.algorithm.permutation_alignment``).
+posterior is formed only when somebody reads it; permutation alignment runs once per call, on the
+device for 2..8 sources (csrc/permutation.hip, route ``device_alignment``) and on the host for 1 or
+9..16 (``ssspy_amd.algorithm.permutation_alignment``).
 
 On the device: 2..8 channels, 1..16 sources, ``flooring_fn`` None / ``max_flooring`` /
 ``add_flooring`` (possibly a ``functools.partial`` with ``eps``); anything else raises
@@ -19,9 +20,11 @@ from typing import Callable, List, Optional, Union
 import numpy as np
 
 from .. import _device as dv
-from .. import _ops
+from .. import _lib, _ops, _routes
 from ..algorithm.permutation_alignment import (
     correlation_based_permutation_solver,
+    device_correlation_permutation,
+    device_score_permutation,
     score_based_permutation_solver,
 )
 from ..special.flooring import identity, max_flooring
@@ -198,7 +201,7 @@ class CACGMMBase(DeviceStateMixin, IterativeMethodBase):
 
         return logdet
 
-    # -- permutation alignment (host, once per call) ---------------------------------------
+    # -- permutation alignment (once per call) ---------------------------------------------
     def solve_permutation(self, flooring_fn="self") -> None:
         """Align the components over the bins by ``permutation_alignment``."""
         permutation_alignment = self.permutation_alignment
@@ -252,6 +255,37 @@ class CACGMMBase(DeviceStateMixin, IterativeMethodBase):
         self._state_set_dev("output", _ops.cacgmm_separate(self._state_dev("posterior"), self._X,
                                                            self.reference_id))
 
+    def _align_on_device(self, solver, target, flooring_fn, **iters) -> bool:
+        """The alignment on the device where route ``device_alignment`` and
+        ``ssspy_permutation_route`` allow (2..8 sources, a built-in floor): the amplitudes
+        ``|gamma x_ref|`` are formed there, mixing, covariance and posterior are gathered there, and
+        only the permutations -- for the correlation solver also the per-bin overlaps -- cross to
+        the host.  False: nothing was done, the host solvers take over."""
+        floor = device_flooring(flooring_fn, allow_host=True)
+        if not _routes.get("device_alignment") or not _ops.permutation_route(
+                self.n_sources, self.n_frames, solver, floor):
+            return False
+        gamma = self._state_dev("posterior")
+        sequence = gamma
+        if target == "amplitude":
+            sequence = _ops.permutation_amplitude(gamma, self._X, self.reference_id)
+        if solver == _lib.PERM_SOLVER_SCORE:
+            perm = device_score_permutation(sequence, floor, **iters)
+        else:
+            perm = device_correlation_permutation(sequence, floor)
+        layout = _lib.PERM_LAYOUT_SOURCE_BIN
+        mixing = _ops.permute_sources(self._state_dev("mixing"), perm, layout)
+        covariance = _ops.permute_sources(self._state_dev("covariance"), perm, layout)
+        gamma = _ops.permute_sources(gamma, perm, layout)
+        self._state_set_dev("mixing", mixing)
+        self._state_set_dev("covariance", covariance)
+        self._state_set_dev("posterior", gamma)
+        self.__dict__["_posterior_from"] = None
+        applied = dv.to_host(perm).astype(np.intp)
+        self._applied_permutation = applied if self._batched else applied[0]
+        self._state_set_dev("output", _ops.cacgmm_separate(gamma, self._X, self.reference_id))
+        return True
+
     def solve_permutation_by_score(self, target: str = "posterior", flooring_fn="self") -> None:
         """Align by the score of Sawada et al. on the posteriors or on the amplitudes."""
         assert target in ["posterior", "amplitude"], "Invalid target {} is specified.".format(
@@ -261,6 +295,10 @@ class CACGMMBase(DeviceStateMixin, IterativeMethodBase):
         flooring_fn = choose_flooring_fn(flooring_fn, method=self)
         global_iter = getattr(self, "global_iter", 1)
         local_iter = getattr(self, "local_iter", 1)
+
+        if self._align_on_device(_lib.PERM_SOLVER_SCORE, target, flooring_fn,
+                                 global_iter=global_iter, local_iter=local_iter):
+            return
 
         alpha, cov, gamma = self._host_parameters()
         ref = self._reference_channel() if target == "amplitude" else None
@@ -287,6 +325,9 @@ class CACGMMBase(DeviceStateMixin, IterativeMethodBase):
         assert target == "amplitude", "Only amplitude is supported as target."
 
         flooring_fn = choose_flooring_fn(flooring_fn, method=self)
+
+        if self._align_on_device(_lib.PERM_SOLVER_CORRELATION, target, flooring_fn):
+            return
 
         alpha, cov, gamma = self._host_parameters()
         ref = self._reference_channel()

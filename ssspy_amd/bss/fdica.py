@@ -21,7 +21,8 @@ problem on its slab of the mixture.  Two paths:
 ``ssspy_fdica_route`` decides between them, once.  User closures follow the compatibility path of
 ``GradIVABase``: ``score_fn`` sees the whole estimate on the host, ``d_contrast_fn`` sees ``|Y|`` on the
 host and the weights go back up, ``contrast_fn`` runs on the host only when the loss is recorded.
-Permutation alignment runs on the host, once per call.
+Permutation alignment runs on the device, once per call (csrc/permutation.hip: 2..8 sources, the
+built-in floors; route ``device_alignment``), and on the host beyond that.
 """
 
 import functools
@@ -31,7 +32,10 @@ import numpy as np
 
 from .. import _device as dv
 from .. import _lib, _ops, _routes
-from ..algorithm.permutation_alignment import correlation_based_permutation_solver
+from ..algorithm.permutation_alignment import (
+    correlation_based_permutation_solver,
+    device_correlation_permutation,
+)
 from ..special.flooring import identity, max_flooring
 from ..utils.flooring import choose_flooring_fn, device_flooring, host_floor
 from ..utils.select_pair import resolve_pairs, sequential_pair_selector
@@ -181,7 +185,7 @@ class FDICABase(DemixingFilterBase):
         _, logdet = np.linalg.slogdet(demix_filter)
         return logdet
 
-    # -- permutation alignment (host, once per call) ---------------------------------------------
+    # -- permutation alignment (once per call) ---------------------------------------------------
     def solve_permutation(self) -> None:
         """ref: ssspy/bss/fdica.py:239-255."""
         permutation_alignment = self.permutation_alignment
@@ -197,13 +201,24 @@ class FDICABase(DemixingFilterBase):
 
     def solve_permutation_by_correlation(self, flooring_fn="self") -> None:
         """Align the rows of the filters over the bins by the correlation of the amplitude envelopes
-        (ref: ssspy/bss/fdica.py:257-281).  The estimate and the filters come to the host once, the
-        aligned filters go back up; ``output`` follows them when it is read."""
+        (ref: ssspy/bss/fdica.py:257-281).  On the device where ``ssspy_permutation_route`` allows:
+        only the per-bin overlaps come to the host, to be sorted, and the rows of the filters are
+        gathered in place of a round trip.  Otherwise (route ``device_alignment`` off, more than 8
+        sources, a flooring callable) the estimate and the filters come to the host once and the
+        aligned filters go back up.  ``output`` follows the filters when it is read."""
         if flooring_fn is not None:  # (None: the identity, as the solver itself takes it)
             flooring_fn = choose_flooring_fn(flooring_fn, method=self)
         Wd = self._state_dev("demix_filter")
         Yd = _ops.separate(self._X, Wd)
         self._check_device_errors()
+        floor = device_flooring(flooring_fn, allow_host=True)
+        if _routes.get("device_alignment") and _ops.permutation_route(
+                Yd.shape[1], Yd.shape[3], _lib.PERM_SOLVER_CORRELATION, floor):
+            perm = device_correlation_permutation(Yd, floor)
+            self._state_set_dev("demix_filter",
+                                _ops.permute_sources(Wd, perm, _lib.PERM_LAYOUT_BIN_SOURCE))
+            self._filters_stepped()
+            return
         Y, W = dv.to_host(Yd), np.array(dv.to_host(Wd))
         for b in range(Y.shape[0]):
             Yb = np.array(Y[b].transpose(1, 0, 2))  # (n_bins, n_sources, n_frames)
