@@ -13,10 +13,10 @@
 // One source for every source count: NC > 0 compiles the count in (2..8: the working set of a lane
 // is indexed by constants and sits in registers; Jacobi unrolled up to 6 x 6, rolled for 7, 8 as in
 // hermitian.hpp), NC == 0 takes it at run time (9..16, matrices in the lane's private memory as in
-// hermitian_rt.hip / grad_iva.hip -- correct, not tuned).
+// grad_iva.hip -- correct, not tuned).
 #include "common.hpp"
 #include "hermitian.hpp"
-#include "rt_hermitian.hpp"
+#include "rt_dense.hpp"
 
 namespace ssspy {
 
@@ -32,43 +32,18 @@ constexpr int fi_group() {
   return NC == 0 ? RTN : (NC <= 4 ? NC : (NC <= 6 ? 3 : 2));
 }
 
-// cyclic Jacobi on flat row-major matrices: A = P diag(lam) P^H, lam on the diagonal of A.  Every lane
-// of the wave must be in the call (the sweep loop ends on a wave vote).
+// The dimension descriptor (hermitian.hpp) of a source count, for the routines on the flat row-major
+// matrices of a lane; the Jacobi sweeps are rolled (a call, the matrix in private memory) at 7 and 8.
+// Every lane of the wave must be in a call of jacobi (the sweep loop ends on a wave vote).
 template <int NC>
-__device__ __forceinline__ void fi_jacobi(c128 *A, c128 *P, int N) {
-  if constexpr (NC == 0) {
-    rt_jacobi(A, P, N);
-  } else {
-    c128 A2[NC][NC], P2[NC][NC];
-#pragma unroll
-    for (int r = 0; r < NC; ++r)
-#pragma unroll
-      for (int c = 0; c < NC; ++c) A2[r][c] = A[r * NC + c];
-    if constexpr (NC <= 6) jacobi_eigh<NC>(A2, P2);
-    else jacobi_eigh_rolled<NC>(A2, P2);
-#pragma unroll
-    for (int r = 0; r < NC; ++r)
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        A[r * NC + c] = A2[r][c];
-        P[r * NC + c] = P2[r][c];
-      }
-  }
+__device__ __forceinline__ auto fi_dim(int N) {
+  if constexpr (NC == 0) return Runtime{N};
+  else return Fixed<NC>{};
 }
-
 template <int NC>
-__device__ __forceinline__ void fi_hermitize(c128 *A, int N) {
-#pragma unroll
-  for (int a = 0; a < N; ++a) {
-    A[a * N + a] = cmake(A[a * N + a].x, 0.0);
-#pragma unroll
-    for (int b = a + 1; b < N; ++b) {
-      const c128 z = cmake(0.5 * (A[a * N + b].x + A[b * N + a].x),
-                           0.5 * (A[a * N + b].y - A[b * N + a].y));
-      A[a * N + b] = z;
-      A[b * N + a] = cconj(z);
-    }
-  }
+__device__ __forceinline__ auto fi_jacobi_dim(int N) {
+  if constexpr (NC == 0) return Runtime{N};
+  else return Fixed<NC, (NC > 6)>{};
 }
 
 // W <- (W W^H)^-1/2 W, the unitary polar factor u v^H of W = u s v^H (ssspy/bss/iva.py:1204-1205,
@@ -92,7 +67,7 @@ __device__ __forceinline__ bool fi_orthonormalize(c128 *W, int N) {
       G[r * N + c] = s;
       G[c * N + r] = cconj(s);
     }
-  fi_jacobi<NC>(G, P, N);
+  jacobi(fi_jacobi_dim<NC>(N), G, P);
   double w[C];
   double lmin = G[0].x, lmax = G[0].x;
 #pragma unroll
@@ -367,8 +342,8 @@ __global__ __launch_bounds__(64) void k_principal_rows(c128 *W, const c128 *__re
   c128 A[C * C], P[C * C];
 #pragma unroll
   for (int e = 0; e < N * N; ++e) A[e] = U[ln.idx * (N * N) + e];
-  fi_hermitize<NC>(A, N);
-  fi_jacobi<NC>(A, P, N);
+  hermitize(fi_dim<NC>(N), A);
+  jacobi(fi_jacobi_dim<NC>(N), A, P);
   int best = 0;
   double lbest = A[0].x;
   bool finite = true;
@@ -410,8 +385,8 @@ __global__ __launch_bounds__(64) void k_whitening_filter(const c128 *__restrict_
   c128 A[C * C], P[C * C];
 #pragma unroll
   for (int e = 0; e < N * N; ++e) A[e] = Cm[ln.idx * (N * N) + e];
-  fi_hermitize<NC>(A, N);
-  fi_jacobi<NC>(A, P, N);
+  hermitize(fi_dim<NC>(N), A);
+  jacobi(fi_jacobi_dim<NC>(N), A, P);
   if (!ln.live) return;
   bool ok = true;
 #pragma unroll

@@ -669,7 +669,7 @@ __global__ __launch_bounds__(128) void k_separate(const c128 *__restrict__ X,
         sm[m] = cmake(y.x * g, y.y * g);
       }
     } else if constexpr (REPAIR) {
-      // (A and P live in the lane's scratch memory: jacobi_eigh_rolled indexes them at run time.
+      // (A and P live in the lane's scratch memory: the rolled jacobi_eigh indexes them at run time.
       //  Unrolled on registers this branch spilled 530-2 400 VGPRs at 5-8 channels.)
       c128 A[M][M], P[M][M];
 #pragma unroll 1
@@ -697,7 +697,7 @@ __global__ __launch_bounds__(128) void k_separate(const c128 *__restrict__ X,
           for (int a = 0; a < M; ++a) P[a][k] = P_io[(point * M + a) * M + k];
         }
       } else {
-        jacobi_eigh_rolled<M>(A, P);
+        jacobi_eigh<M, true>(A, P);
 #pragma unroll
         for (int k = 0; k < M; ++k) evs[k] = apply_floor(A[k][k].x, floor_kind, eps);
       }

@@ -23,7 +23,8 @@
 // replaces: ssspy/bss/mnmf.py:1278-1303 (update_once), :1305-1417, :1449-1514, :1635-1675, :632-678,
 //           :1219-1261 (loss), :1174-1217 (Wiener filter) for the shapes above.
 #include "common.hpp"
-#include "rt_hermitian.hpp"
+#include "hermitian.hpp"
+#include "rt_dense.hpp"
 #include "ssspy_amd.h"
 
 namespace ssspy {
@@ -544,7 +545,7 @@ __global__ __launch_bounds__(64) void k_repair_rt(const c128 *__restrict__ X,
   __syncthreads();
   double qf2 = 0.0;
   for (int e = 0; e < M * M; ++e) qf2 += cabs2(qsrc[e]);
-  // every lane walks the same number of rounds (rt_jacobi ends its sweeps on a wave vote)
+  // every lane walks the same number of rounds (jacobi ends its sweeps on a wave vote)
   for (int j0 = 0; j0 < T; j0 += 64) {
     const bool valid = j0 + (int)threadIdx.x < T;
     const int j = valid ? j0 + threadIdx.x : T - 1;
@@ -595,7 +596,7 @@ __global__ __launch_bounds__(64) void k_repair_rt(const c128 *__restrict__ X,
           A[a * M + c2] = s;
           A[c2 * M + a] = cconj(s);
         }
-      rt_jacobi(A, P, M);
+      jacobi(Runtime{M}, A, P);
       for (int k = 0; k < M; ++k) evs[k] = apply_floor(A[k * M + k].x, floor_kind, eps);
     }
     if (EIG == 1) {

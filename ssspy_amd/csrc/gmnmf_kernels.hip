@@ -683,19 +683,6 @@ __global__ __launch_bounds__(GM_PB) void k_gmnmf_spatial_acc(const c128 *__restr
 // unrolled on registers the kernel spilled 136-5 858 VGPRs at 5-8 channels; it runs for flagged
 // blocks only)
 template <int M>
-__device__ __forceinline__ void su_matmul(const c128 (&A)[M][M], const c128 (&B)[M][M],
-                                          c128 (&C)[M][M]) {
-  if constexpr (M >= 5) matmul_rolled<M>(A, B, C);
-  else matmul<M>(A, B, C);
-}
-template <int M>
-__device__ __forceinline__ void su_rebuild(const c128 (&P)[M][M], const double (&w)[M],
-                                           c128 (&Out)[M][M]) {
-  if constexpr (M >= 5) herm_rebuild_rolled<M>(P, w, Out);
-  else herm_rebuild<M>(P, w, Out);
-}
-
-template <int M>
 __global__ __launch_bounds__(64) void k_gmnmf_spatial_update(c128 *H,
                                                              const double *__restrict__ PQacc,
                                                              long long count, int floor_kind,
@@ -704,6 +691,7 @@ __global__ __launch_bounds__(64) void k_gmnmf_spatial_update(c128 *H,
   if (flags && !flags[blockIdx.x]) return;
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= count) return;
+  constexpr bool SU_ROLLED = M >= 5;
   c128 Hm[M][M], Qm[M][M], Tm[M][M], C[M][M], Pv[M][M];
   double lam[M], w[M];
 #pragma unroll
@@ -712,35 +700,34 @@ __global__ __launch_bounds__(64) void k_gmnmf_spatial_update(c128 *H,
     for (int c = 0; c < M; ++c) Hm[a][c] = H[idx * (M * M) + a * M + c];
   unpack_hermitian<M>(PQacc + idx * (2 * M * M) + M * M, Qm);
   // HQH, floored
-  su_matmul<M>(Hm, Qm, Tm);
-  su_matmul<M>(Tm, Hm, C);
-  psd_eigen<M, (M >= 5)>(C, Pv, lam, floor_kind, eps);
+  matmul<M, SU_ROLLED>(Hm, Qm, Tm);
+  matmul<M, SU_ROLLED>(Tm, Hm, C);
+  psd_eigen<M, SU_ROLLED>(C, Pv, lam, floor_kind, eps);
   c128 HQH[M][M];
-  su_rebuild<M>(Pv, lam, HQH);
+  herm_rebuild<M, SU_ROLLED>(Pv, lam, HQH);
   // P floored, P^(1/2), P^(-1/2)
   unpack_hermitian<M>(PQacc + idx * (2 * M * M), C);
-  psd_eigen<M, (M >= 5)>(C, Pv, lam, floor_kind, eps);
+  psd_eigen<M, SU_ROLLED>(C, Pv, lam, floor_kind, eps);
   c128 Ph[M][M], Pih[M][M];
 #pragma unroll
   for (int k = 0; k < M; ++k) w[k] = sqrt(lam[k]);
-  su_rebuild<M>(Pv, w, Ph);
+  herm_rebuild<M, SU_ROLLED>(Pv, w, Ph);
 #pragma unroll
   for (int k = 0; k < M; ++k) w[k] = 1.0 / w[k];
-  su_rebuild<M>(Pv, w, Pih);
+  herm_rebuild<M, SU_ROLLED>(Pv, w, Pih);
   // (P^1/2 HQH P^1/2)^1/2
-  su_matmul<M>(Ph, HQH, Tm);
-  su_matmul<M>(Tm, Ph, C);
+  matmul<M, SU_ROLLED>(Ph, HQH, Tm);
+  matmul<M, SU_ROLLED>(Tm, Ph, C);
   hermitize<M>(C);
-  if constexpr (M >= 5) jacobi_eigh_rolled<M>(C, Pv);
-  else jacobi_eigh<M>(C, Pv);
+  jacobi_eigh<M, SU_ROLLED>(C, Pv);
 #pragma unroll
   for (int k = 0; k < M; ++k) w[k] = sqrt(fmax(C[k][k].x, 0.0));
-  su_rebuild<M>(Pv, w, Qm);
+  herm_rebuild<M, SU_ROLLED>(Pv, w, Qm);
   // G = P^-1/2 (...) P^-1/2, floored
-  su_matmul<M>(Pih, Qm, Tm);
-  su_matmul<M>(Tm, Pih, C);
-  psd_eigen<M, (M >= 5)>(C, Pv, lam, floor_kind, eps);
-  su_rebuild<M>(Pv, lam, Hm);
+  matmul<M, SU_ROLLED>(Pih, Qm, Tm);
+  matmul<M, SU_ROLLED>(Tm, Pih, C);
+  psd_eigen<M, SU_ROLLED>(C, Pv, lam, floor_kind, eps);
+  herm_rebuild<M, SU_ROLLED>(Pv, lam, Hm);
 #pragma unroll
   for (int a = 0; a < M; ++a)
 #pragma unroll

@@ -13,7 +13,7 @@
 #include "hermitian.hpp"
 #include "ipa_common.hpp"
 #include "rt_dense.hpp"
-#include "rt_hermitian.hpp"
+#include "rt_dense.hpp"
 #include "ssspy_amd.h"
 
 namespace ssspy {
@@ -73,7 +73,7 @@ template <bool FUSED, class Vote>
 __device__ void rt_lqpqm2(c128 *H, c128 *sigma, const c128 *v, double z, int L, int floor_kind,
                           double eps, int max_iter, c128 *y, Vote vote,
                           int singular_override = -1) {
-  rt_jacobi(H, sigma, L);
+  jacobi(Runtime{L}, H, sigma);
   double phi[RN], ph[RN], w2[RN];
   c128 vt[RN];
   for (int l = 0; l < L; ++l) phi[l] = H[l * L + l].x;
@@ -196,14 +196,14 @@ __device__ void rt_ipa_step(c128 *Vc, c128 *G, long long bin, bool live, int N, 
   for (int mm = 0; mm < L; ++mm) {
     const int m = rest_rt(S, mm);
     for (int e = 0; e < N * N; ++e) M[e] = Ub[m * N * N + e];
-    rt_hermitize(M, N);
+    hermitize(Runtime{N}, M);
     double ass = M[S * N + S].x;
     c128 bsm = M[S * N + m];
     bool idle = floor_kind != SSSPY_FLOOR_MAX;
     if (floor_kind == SSSPY_FLOOR_ADD) ass += eps;
     if (floor_kind == SSSPY_FLOOR_MAX) idle = rt_shifted_pd(M, P, N, eps);
     if (!idle) {  // (the sweeps end on a test over the lanes that are here: __all sees the active ones)
-      rt_psd_eigen(M, P, lam, N, floor_kind, eps);
+      psd_eigen(Runtime{N}, M, P, lam, floor_kind, eps);
       ass = 0.0;
       bsm = cmake(0.0, 0.0);
       for (int k = 0; k < N; ++k) {
@@ -218,7 +218,7 @@ __device__ void rt_ipa_step(c128 *Vc, c128 *G, long long bin, bool live, int N, 
   }
   // U_S: to_psd, then _psd_inv floors the floored eigenvalues again
   for (int e = 0; e < N * N; ++e) M[e] = Ub[S * N * N + e];
-  rt_hermitize(M, N);
+  hermitize(Runtime{N}, M);
   bool literal = floor_kind == SSSPY_FLOOR_MAX && !rt_shifted_pd(M, P, N, eps);
   if (!literal) {
     for (int r = 0; r < N; ++r)
@@ -226,12 +226,13 @@ __device__ void rt_ipa_step(c128 *Vc, c128 *G, long long bin, bool live, int N, 
         P[r * N + c] = (r == c && floor_kind == SSSPY_FLOOR_ADD)
                            ? cmake(M[r * N + c].x + 2.0 * eps, 0.0)
                            : M[r * N + c];
-    literal = !rt_chol_inverse(P, Uinv, X1, N);
+    double ld;
+    literal = !chol_inverse(Runtime{N}, P, Uinv, X1, ld);
   }
   if (literal) {
-    rt_psd_eigen(M, P, lam, N, floor_kind, eps);
+    psd_eigen(Runtime{N}, M, P, lam, floor_kind, eps);
     for (int k = 0; k < N; ++k) w[k] = 1.0 / apply_floor(lam[k], floor_kind, eps);
-    rt_rebuild(P, w, Uinv, N);
+    rebuild(Runtime{N}, P, w, Uinv);
   }
   // C = conj(Uinv)[rest][rest] (X1: L x L, kept; X2: the copy the solver destroys), d, z
   for (int r = 0; r < L; ++r) {
@@ -263,7 +264,7 @@ __device__ void rt_ipa_step(c128 *Vc, c128 *G, long long bin, bool live, int N, 
     for (int e = 0; e < L * L; ++e) X2[e] = cscale(X2[e], it);
     z *= it;
   }
-  rt_hermitize(X2, L);
+  hermitize(Runtime{L}, X2);
   rt_lqpqm2<FUSED, Vote>(X2, X1, v, z, L, floor_kind, eps, max_iter, qc, vote);
   // q = q_check / a_sqrt - b / a ; q~ = e_S - E conj(q)
   for (int r = 0; r < L; ++r)
@@ -273,13 +274,14 @@ __device__ void rt_ipa_step(c128 *Vc, c128 *G, long long bin, bool live, int N, 
   // Uq = U_S^-1 q~ (single floor), p = Uq / floor(sqrt(max(q~^H Uq, 0)))
   if (literal) {
     for (int k = 0; k < N; ++k) w[k] = 1.0 / lam[k];
-    rt_rebuild(P, w, Uinv, N);
+    rebuild(Runtime{N}, P, w, Uinv);
   } else if (floor_kind == SSSPY_FLOOR_ADD) {
     // (M still holds the Hermitian part of U_S: the singly floored inverse is (A + eps I)^-1)
     for (int r = 0; r < N; ++r)
       for (int c = 0; c < N; ++c)
         P[r * N + c] = r == c ? cmake(M[r * N + c].x + eps, 0.0) : M[r * N + c];
-    if (!rt_chol_inverse(P, Uinv, X1, N) && info && live) atomicAdd(info, 1);
+    double ld;
+    if (!chol_inverse(Runtime{N}, P, Uinv, X1, ld) && info && live) atomicAdd(info, 1);
   }
   double quq = 0.0;
   for (int r = 0; r < N; ++r) {
@@ -401,13 +403,13 @@ __global__ __launch_bounds__(64) void k_lqpqm2_rt(const c128 *__restrict__ H,
                                                   const int *__restrict__ singular) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const bool live = i < n;
-  const long long idx = live ? i : n - 1;  // (every lane is in rt_jacobi's wave votes)
+  const long long idx = live ? i : n - 1;  // (every lane is in jacobi's wave votes)
   c128 Hm[RN * RN], sigma[RN * RN], vv[RN], yy[RN];
   for (int r = 0; r < L; ++r) {
     vv[r] = v[idx * L + r];
     for (int c = 0; c < L; ++c) Hm[r * L + c] = H[(idx * L + r) * L + c];
   }
-  rt_hermitize(Hm, L);
+  hermitize(Runtime{L}, Hm);
   const int so = singular ? singular[idx] : -1;
   if (MODE == NEWTON_FIXED) {
     rt_lqpqm2<false, NoVoteRt>(Hm, sigma, vv, z[idx], L, floor_kind, eps, max_iter, yy, NoVoteRt(),

@@ -71,8 +71,7 @@ __device__ __noinline__ void psd_repair(c128 (&R)[L][L]) {
     c128 P[L][L];
     double lam[L];
     psd_eigen<L, (L > 4)>(R, P, lam, SSSPY_FLOOR_MAX, IPSDTA_PSD_EPS);
-    if constexpr (L > 4) herm_rebuild_rolled<L>(P, lam, R);
-    else herm_rebuild<L>(P, lam, R);
+    herm_rebuild<L, (L > 4)>(P, lam, R);
   }
 }
 

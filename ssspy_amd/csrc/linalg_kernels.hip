@@ -4,22 +4,12 @@
 
 #include "common.hpp"
 #include "eigh2.hpp"
-#include "hermitian.hpp"
 #include "herm_packed.hpp"
+#include "hermitian_entry.hpp"
+#include "rt_dense.hpp"
 #include "smallmat.hpp"
 
 namespace ssspy {
-
-// hermitian_rows.hip
-bool hermitian_rows_wanted(int M, int always_from);
-int eigh_rows(const void *A, double *lamb, void *V, long long n, int M, int mode, int floor_kind,
-              double eps, hipStream_t st);
-// hermitian_rt.hip: 9 x 9 .. 16 x 16, the size at run time
-bool hermitian_rt_wanted(int M);
-int solve_rt(const void *A, const void *Bm, void *X, long long n, int M, int nrhs, int *info,
-             hipStream_t st);
-int eigh_rt(const void *A, double *lamb, void *V, long long n, int M, int mode, int floor_kind,
-            double eps, hipStream_t st);
 
 // X = A^-1 B, B (N x nrhs)
 template <int N>
@@ -45,6 +35,27 @@ __global__ __launch_bounds__(64) void k_solve(const c128 *__restrict__ A, const 
   if (!ok && info) atomicAdd(info, 1);
 }
 
+// The same with the size at run time (9..16) by LU with partial pivoting on private memory; the
+// right-hand sides pass through in chunks of M columns
+__global__ __launch_bounds__(64) void k_solve_rt(const c128 *__restrict__ A,
+                                                 const c128 *__restrict__ Bm, c128 *X, long long n,
+                                                 int M, int nrhs, int *info) {
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n) return;
+  c128 Am[RTN * RTN], Inv[RTN * RTN];
+  load_matrix(Runtime{M}, Am, A, idx);
+  for (int r = 0; r < M; ++r)
+    for (int c = 0; c < M; ++c) Inv[r * M + c] = cmake(r == c ? 1.0 : 0.0, 0.0);
+  const bool ok = rt_lu_solve(Am, Inv, M, M);
+  for (int c = 0; c < nrhs; ++c)
+    for (int r = 0; r < M; ++r) {
+      c128 acc = cmake(0.0, 0.0);
+      for (int k = 0; k < M; ++k) cfma(acc, Inv[r * M + k], Bm[(idx * M + k) * nrhs + c]);
+      X[(idx * M + r) * nrhs + c] = acc;
+    }
+  if (!ok && info) atomicAdd(info, 1);
+}
+
 // closed-form 2x2 inverse (no pivoting), ref: ssspy/linalg/inv.py:4-54
 __global__ __launch_bounds__(256) void k_inv2(const c128 *__restrict__ A, c128 *out, long long n) {
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -59,52 +70,46 @@ __global__ __launch_bounds__(256) void k_inv2(const c128 *__restrict__ A, c128 *
 
 // Hermitian eigen-decomposition, eigenvalues ascending (as numpy.linalg.eigh), unit eigenvectors.
 // mode 0: write lamb (n, M) and V (n, M, M);  mode 1 (to_psd): floor eigenvalues, rebuild into V.
-template <int M>
-__global__ __launch_bounds__(64) void k_eigh(const c128 *__restrict__ A, double *lamb, c128 *V,
+template <class D>
+__global__ __launch_bounds__(64) void k_eigh(D d, const c128 *__restrict__ A, double *lamb, c128 *V,
                                              long long n, int mode, int floor_kind, double eps) {
-  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= n) return;
-  c128 Am[M][M], P[M][M];
-#pragma unroll
-  for (int r = 0; r < M; ++r)
-#pragma unroll
-    for (int c = 0; c < M; ++c) Am[r][c] = A[(idx * M + r) * M + c];
-  hermitize<M>(Am);
-  jacobi_eigh<M>(Am, P);
+  const int M = d.n();
+  const HermLane ln = herm_lane(n);
+  if (!D::shadows_tail && !ln.live) return;
+  c128 Am[D::cap * D::cap], P[D::cap * D::cap];
+  load_matrix(d, Am, A, ln.idx);
+  hermitize(d, Am);
+  jacobi(d, Am, P);
+  if (!ln.live) return;
   if (mode == 0) {
-    // rank of every eigenvalue (ties broken by index) -> ascending order without dynamic indexing
-#pragma unroll
-    for (int k = 0; k < M; ++k) {
-      int rank = 0;
-#pragma unroll
-      for (int j = 0; j < M; ++j)
-        rank += (Am[j][j].x < Am[k][k].x || (Am[j][j].x == Am[k][k].x && j < k)) ? 1 : 0;
-      lamb[idx * M + rank] = Am[k][k].x;
-#pragma unroll
-      for (int r = 0; r < M; ++r) V[(idx * M + r) * M + rank] = P[r][k];
-    }
-  } else {
-    c128 R[M][M];
-#pragma unroll
+    store_sorted(d, Am, P, lamb, V, ln.idx);
+    return;
+  }
+  c128 R[D::cap * D::cap];
+  if constexpr (D::psd_full_rebuild) {
+    // every entry's own sum, then the average with the adjoint: its imaginary parts round otherwise
+    // than the mirrored upper triangle of rebuild(), and the compiled-in sizes have always had these
+#pragma unroll D::unroll
     for (int r = 0; r < M; ++r)
-#pragma unroll
+#pragma unroll D::unroll
       for (int c = 0; c < M; ++c) {
         c128 acc = cmake(0.0, 0.0);
-#pragma unroll
+#pragma unroll D::unroll
         for (int k = 0; k < M; ++k) {
-          const double ev = apply_floor(Am[k][k].x, floor_kind, eps);
-          const c128 z = cmulc(P[r][k], P[c][k]);
+          const double ev = apply_floor(Am[k * M + k].x, floor_kind, eps);
+          const c128 z = cmulc(P[r * M + k], P[c * M + k]);
           acc.x = fma(ev, z.x, acc.x);
           acc.y = fma(ev, z.y, acc.y);
         }
-        R[r][c] = acc;
+        R[r * M + c] = acc;
       }
-    hermitize<M>(R);
-#pragma unroll
-    for (int r = 0; r < M; ++r)
-#pragma unroll
-      for (int c = 0; c < M; ++c) V[(idx * M + r) * M + c] = R[r][c];
+    hermitize(d, R);
+  } else {
+    double w[D::cap];
+    for (int k = 0; k < M; ++k) w[k] = apply_floor(Am[k * M + k].x, floor_kind, eps);
+    rebuild(d, P, w, R);
   }
+  store_matrix(d, V, R, ln.idx);
 }
 
 // The same for 6-8 x 6-8 on packed storage (herm_packed.hpp): the matrix being diagonalised takes M^2
@@ -341,8 +346,12 @@ int ssspy_herm_rebuild(const void *P, const double *w, void *out, long long n, i
 int ssspy_solve(const void *A, const void *Bm, void *X, long long n, int N, int nrhs, int *info,
                 void *stream) {
   SSSPY_REQUIRE(A && Bm && X && n > 0 && nrhs > 0, "solve: bad argument");
-  if (hermitian_rt_wanted(N)) return solve_rt(A, Bm, X, n, N, nrhs, info, as_stream(stream));
-  dim3 grid((unsigned)((n + 63) / 64)), block(64);
+  dim3 grid = herm_lanes_grid(n), block(64);
+  if (hermitian_rt_wanted(N)) {
+    hipLaunchKernelGGL(k_solve_rt, grid, block, 0, as_stream(stream), (const c128 *)A,
+                       (const c128 *)Bm, (c128 *)X, n, N, nrhs, info);
+    return check_launch("k_solve_rt");
+  }
   DISPATCH_N(N, hipLaunchKernelGGL((k_solve<NN>), grid, block, 0, as_stream(stream),
                                    (const c128 *)A, (const c128 *)Bm, (c128 *)X, n, nrhs, info));
   return check_launch("k_solve");
@@ -368,50 +377,57 @@ int ssspy_inv2(const void *A, void *out, long long n, void *stream) {
     default: return ::ssspy::fail(SSSPY_ERR_UNSUPPORTED, "eigh: size must be in [1, 16]");         \
   }
 
+// mode 0 (eigh) / mode 1 (to_psd) on the lane-per-matrix kernel, the size at run time or compiled in
+static int eigh_lanes(HermRoute route, const void *A, double *lamb, void *V, long long n, int M,
+                      int mode, int floor_kind, double eps, hipStream_t st, const char *what) {
+  const dim3 grid = herm_lanes_grid(n), block(64);
+  if (route == HermRoute::RUNTIME) {
+    hipLaunchKernelGGL((k_eigh<Runtime>), grid, block, 0, st, Runtime{M}, (const c128 *)A, lamb,
+                       (c128 *)V, n, mode, floor_kind, eps);
+    return check_launch("k_eigh_rt");
+  }
+  SSSPY_DISPATCH_EIGH5(M, hipLaunchKernelGGL((k_eigh<Fixed<NN>>), grid, block, 0, st, Fixed<NN>{},
+                                             (const c128 *)A, lamb, (c128 *)V, n, mode, floor_kind,
+                                             eps));
+  return check_launch(what);
+}
+
 int ssspy_eigh(const void *A, double *lamb, void *V, long long n, int M, void *stream) {
   SSSPY_REQUIRE(A && lamb && V && n > 0, "eigh: bad argument");
-  if (hermitian_rt_wanted(M)) return eigh_rt(A, lamb, V, n, M, 0, 0, 0.0, as_stream(stream));
-  if (M == 2) {
+  const HermRoute route = hermitian_route(M, true, true);
+  if (route == HermRoute::CLOSED2) {
     hipLaunchKernelGGL(k_eigh2_plain, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                        as_stream(stream), (const c128 *)A, lamb, (c128 *)V, n);
     return check_launch("k_eigh2_plain");
   }
-  if (hermitian_rows_wanted(M, 7))
-    return eigh_rows(A, lamb, V, n, M, 0, 0, 0.0, as_stream(stream));
-  dim3 grid((unsigned)((n + 63) / 64)), block(64);
-  if (M == 6) {  // packed storage
-    hipLaunchKernelGGL((k_eigh_p<6>), grid, block, 0, as_stream(stream), (const c128 *)A, lamb,
-                       (c128 *)V, n, 0, 0, 0.0);
+  if (route == HermRoute::ROWS8) return eigh_rows(A, lamb, V, n, M, 0, 0, 0.0, as_stream(stream));
+  if (route == HermRoute::PACKED6) {
+    hipLaunchKernelGGL((k_eigh_p<6>), herm_lanes_grid(n), dim3(64), 0, as_stream(stream),
+                       (const c128 *)A, lamb, (c128 *)V, n, 0, 0, 0.0);
     return check_launch("k_eigh_p");
   }
-  SSSPY_DISPATCH_EIGH5(M, hipLaunchKernelGGL((k_eigh<NN>), grid, block, 0, as_stream(stream),
-                                             (const c128 *)A, lamb, (c128 *)V, n, 0, 0, 0.0));
-  return check_launch("k_eigh");
+  return eigh_lanes(route, A, lamb, V, n, M, 0, 0, 0.0, as_stream(stream), "k_eigh");
 }
 
 int ssspy_to_psd(const void *A, void *out, long long n, int M, int floor_kind, double floor_eps,
                  void *stream) {
   SSSPY_REQUIRE(A && out && n > 0, "to_psd: bad argument");
-  if (hermitian_rt_wanted(M))
-    return eigh_rt(A, nullptr, out, n, M, 1, floor_kind, floor_eps, as_stream(stream));
-  if (hermitian_rows_wanted(M, 7))
+  const HermRoute route = hermitian_route(M, false, true);
+  if (route == HermRoute::ROWS8)
     return eigh_rows(A, nullptr, out, n, M, 1, floor_kind, floor_eps, as_stream(stream));
-  dim3 grid((unsigned)((n + 63) / 64)), block(64);
-  if (M == 6) {
+  if (route == HermRoute::PACKED6) {
     const size_t smem = (size_t)M * M * EIGH_LD * sizeof(c128);
     if (smem > 48 * 1024) {
       hipError_t e = hipFuncSetAttribute((const void *)k_eigh_p<6>,
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
       if (e != hipSuccess) return fail(SSSPY_ERR_HIP, hipGetErrorString(e));
     }
-    hipLaunchKernelGGL((k_eigh_p<6>), grid, block, smem, as_stream(stream), (const c128 *)A,
-                       (double *)nullptr, (c128 *)out, n, 1, floor_kind, floor_eps);
+    hipLaunchKernelGGL((k_eigh_p<6>), herm_lanes_grid(n), dim3(64), smem, as_stream(stream),
+                       (const c128 *)A, (double *)nullptr, (c128 *)out, n, 1, floor_kind, floor_eps);
     return check_launch("k_to_psd_p");
   }
-  SSSPY_DISPATCH_EIGH5(M, hipLaunchKernelGGL((k_eigh<NN>), grid, block, 0, as_stream(stream),
-                                             (const c128 *)A, (double *)nullptr, (c128 *)out, n, 1,
-                                             floor_kind, floor_eps));
-  return check_launch("k_to_psd");
+  return eigh_lanes(route, A, nullptr, out, n, M, 1, floor_kind, floor_eps, as_stream(stream),
+                    "k_to_psd");
 }
 
 int ssspy_eigh2(const void *A, const void *Bm, double *lamb, void *Z, long long n, int type,

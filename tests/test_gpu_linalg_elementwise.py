@@ -52,7 +52,7 @@ HERM_SIZES = [m for m in lr.SIZES if m >= 2]
 
 
 def eigh_route(M):
-    return {1: "k_eigh<1>", 2: "k_eigh2_plain", 3: "k_eigh<3>", 5: "k_eigh<5>", 6: "k_eigh_p<6>",
+    return {1: "k_eigh<Fixed<1>>", 2: "k_eigh2_plain", 3: "k_eigh<Fixed<3>>", 5: "k_eigh<Fixed<5>>", 6: "k_eigh_p<6>",
             7: "8 lanes padded M7", 8: "8 lanes M8"}.get(M, "run-time M{}".format(M))
 
 

@@ -2049,8 +2049,8 @@ def test_gmeanmh(type):
 def test_hermitian_operators_at_6_to_16_channels_against_lapack(M):
     """eigh, to_psd, the generalised eigenproblem, sqrtmh / invsqrtmh and gmeanmh at 6 x 6 (a lane
     per matrix), 7 x 7 / 8 x 8 (a matrix on 8 lanes, hermitian_rows.hip) and 9 x 9 .. 16 x 16 (the
-    size at run time, hermitian_rt.hip) against LAPACK and the defining identities; eigenvectors
-    through the projectors z z^H (free of the phase each decomposition leaves)."""
+    size at run time, the Runtime kernels of hermitian_ops.hip / linalg_kernels.hip) against LAPACK
+    and the defining identities; eigenvectors through the projectors z z^H (free of the phase each decomposition leaves)."""
     from ssspy_amd.linalg import eigh, gmeanmh, invsqrtmh, sqrtmh
     from ssspy_amd.special.flooring import max_flooring
     from ssspy_amd.special.psd import to_psd
