@@ -891,6 +891,28 @@ int ssspy_hva_dual_step(const void *X, const void *W2, void *dual_q, long long d
                         const double *varrho, double attenuation, double relaxation, int B, int N,
                         int F, int T, void *stream);
 
+/* MaskingADMMHVA: the same mask inside the auxiliary step of MaskingADMMBSS, on ADMM's operand
+ * Z = relaxation W x + (1 - relaxation) aux2_q + dual2_q (aux2_q is not read when relaxation == 1).
+ * (Added at SSSPY_ABI_VERSION 11 without a bump: no existing argument list changed.) */
+
+/* The cepstral pass of ssspy_hva_cepstrum over that Z: one kernel body, the other former of Z.
+ * W (B,F,N,N) the demixing filters of ssspy_admmbss_filter_step; aux2_q != dual2_q, batch_stride at
+ * least N F T; table, varrho, the floor, mask_iter, route and the limits as ssspy_hva_cepstrum.
+ * replaces: ssspy/bss/admmbss.py:415-442 (its Z) with ssspy/bss/hva.py:202-232. */
+int ssspy_hva_admm_cepstrum(const void *X, const void *W, const void *aux2_q, const void *dual2_q,
+                            long long batch_stride, const double *table, double *varrho, int B, int N,
+                            int F, int T, double relaxation, int floor_kind, double floor_eps,
+                            int mask_iter, int route, void *stream);
+
+/* The masked auxiliary step: per (b, f, t) Z again, the mask of ssspy_hva_dual_step from varrho,
+ * aux2_q <- mask Z and dual2_q <- Z - aux2_q in place, both from the registers that hold Z.  A NaN
+ * in varrho (a log 0 column without a floor) gives NaN in both for every source of that frame, as the
+ * reference's sum over sources does.  Checks as ssspy_admmbss_aux_step.
+ * replaces: ssspy/bss/admmbss.py:415-442 (:436, :438) with ssspy/bss/hva.py:233-236. */
+int ssspy_hva_aux_step(const void *X, const void *W, void *aux2_q, void *dual2_q,
+                       long long batch_stride, const double *varrho, double attenuation,
+                       double relaxation, int B, int N, int F, int T, void *stream);
+
 /* ------------------------------------------------- FastIVA / FasterIVA, whitening, PCA */
 
 /* The fixed-point IVA classes work on the whitened mixture Z (B,N,F,T) with unitary filters W

@@ -178,6 +178,9 @@ PROTOTYPES = {
     "ssspy_hva_cos_table": (_i, [_p, _i, _p]),
     "ssspy_hva_cepstrum": (_i, [_p, _p, _p, _q, _p, _p, _i, _i, _i, _i, _i, _d, _i, _i, _p]),
     "ssspy_hva_dual_step": (_i, [_p, _p, _p, _q, _p, _d, _d, _i, _i, _i, _i, _p]),
+    "ssspy_hva_admm_cepstrum": (_i, [_p, _p, _p, _p, _q, _p, _p, _i, _i, _i, _i, _d, _i, _d, _i, _i,
+                                     _p]),
+    "ssspy_hva_aux_step": (_i, [_p, _p, _p, _p, _q, _p, _d, _d, _i, _i, _i, _i, _p]),
     "ssspy_fast_iva_weights": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _d, _p]),
     "ssspy_fast_iva_stats": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "ssspy_fast_iva_step": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p]),

@@ -997,6 +997,31 @@ def hva_dual_step(X, W2, dual, q, varrho, attenuation, relaxation):
     return dual
 
 
+def hva_admm_cepstrum(X, W, aux2, dual2, q, table, flooring, mask_iter, relaxation,
+                      route=_lib.HVA_ROUTE_AUTO, out=None):
+    """varrho (B, N, F, T) f64 of Z = relaxation W x + (1 - relaxation) aux2_q + dual2_q: the pass of
+    ``hva_cepstrum`` on ADMM's operand (aux2_q is not read at relaxation 1)."""
+    aq, dq, stride, (B, N, F, T) = _admm_slices(aux2, dual2, q)
+    assert tuple(table.shape) == (2 * (F - 1),)
+    if out is None:
+        out = dv.empty((B, N, F, T), dv.f64, X.device)
+    assert tuple(out.shape) == (B, N, F, T)
+    _lib.check(_L().ssspy_hva_admm_cepstrum(ptr(X), ptr(W), aq, dq, stride, ptr(table), ptr(out), B, N,
+                                            F, T, float(relaxation), flooring[0], float(flooring[1]),
+                                            int(mask_iter), int(route), _st()), "hva_admm_cepstrum")
+    return out
+
+
+def hva_aux_step(X, W, aux2, dual2, q, varrho, attenuation, relaxation):
+    """aux2_q <- mask Z, dual2_q <- Z - aux2_q in place with Z as in ``hva_admm_cepstrum`` and the mask
+    of ``hva_dual_step``."""
+    aq, dq, stride, (B, N, F, T) = _admm_slices(aux2, dual2, q)
+    assert tuple(varrho.shape) == (B, N, F, T)
+    _lib.check(_L().ssspy_hva_aux_step(ptr(X), ptr(W), aq, dq, stride, ptr(varrho), float(attenuation),
+                                       float(relaxation), B, N, F, T, _st()), "hva_aux_step")
+    return aux2, dual2
+
+
 # --------------------------------------------------------------- FastIVA / FasterIVA, whitening
 def fast_iva_weights(r2, d_contrast, dd_contrast, flooring, want_psi=True):
     """(phi, psi) (B, N, T) from the frame powers and the closures' values on the norms; psi None

@@ -12,7 +12,7 @@ from .fdica import (
     NaturalGradFDICA,
     NaturalGradLaplaceFDICA,
 )
-from .hva import HVA, MaskingPDSHVA
+from .hva import HVA, MaskingADMMHVA, MaskingPDSHVA
 from .ica import FastICA, GradICA, GradLaplaceICA, NaturalGradICA, NaturalGradLaplaceICA
 from .ipsdta import TIPSDTA, BlockDecompositionIPSDTABase, GaussIPSDTA, IPSDTABase
 from .pdsbss import PDSBSS, MaskingPDSBSS, PDSBSSBase
@@ -22,6 +22,6 @@ __all__ = ["IterativeMethodBase", "CACGMM", "CACGMMBase", "IPSDTABase", "BlockDe
            "GaussIPSDTA", "TIPSDTA", "FDICABase", "GradFDICABase", "GradFDICA", "NaturalGradFDICA",
            "AuxFDICA", "GradLaplaceFDICA", "NaturalGradLaplaceFDICA", "AuxLaplaceFDICA",
            "ProxBSSBase", "PDSBSSBase", "PDSBSS", "MaskingPDSBSS", "MaskingPDSHVA", "HVA", "ADMMBSSBase", "ADMMBSS",
-           "MaskingADMMBSS", "GradICA", "NaturalGradICA", "FastICA", "GradLaplaceICA",
+           "MaskingADMMBSS", "MaskingADMMHVA", "GradICA", "NaturalGradICA", "FastICA", "GradLaplaceICA",
            "NaturalGradLaplaceICA", "admmbss", "base", "cacgmm",
            "fdica", "hva", "ica", "ilrma", "ipsdta", "iva", "mnmf", "pdsbss", "proxbss"]

@@ -133,33 +133,6 @@ struct AdmmOperand {
   }
 };
 
-// z_n = relax (W x)_n + (1 - relax) a_n + d_n for the N rows of one (bin, frame); Wn: row-major N x N.
-// mix == false (relaxation 1): a is not read, z_n = (W x)_n + d_n.
-template <int G, typename WPtr>
-__device__ __forceinline__ void admm_form_z(c128 (&z)[G], const c128 *__restrict__ Xb, const c128 *Ab,
-                                            const c128 *Db, WPtr Wn, int N, long long FT, int j,
-                                            double relax, bool mix) {
-  c128 x[G];
-#pragma unroll
-  for (int m = 0; m < G; ++m) x[m] = m < N ? Xb[m * FT + j] : cmake(0.0, 0.0);
-  const double om = 1.0 - relax;
-#pragma unroll
-  for (int n = 0; n < G; ++n) {
-    z[n] = cmake(0.0, 0.0);
-    if (n < N) {
-      c128 y = cmake(0.0, 0.0);
-#pragma unroll
-      for (int m = 0; m < G; ++m)
-        if (m < N) cfma(y, Wn[n * N + m], x[m]);
-      if (mix) {
-        const c128 a = Ab[n * FT + j];
-        y = cmake(relax * y.x + om * a.x, relax * y.y + om * a.y);
-      }
-      z[n] = cadd(y, Db[n * FT + j]);
-    }
-  }
-}
-
 // ---- the group norms of l21 over bins: part[c,b,n,j] = sum over the bins of chunk c of |Z|^2, in
 // bin order.  grid (ceil(T / 256), C, B); a thread owns one frame.  No barriers.
 template <int G>

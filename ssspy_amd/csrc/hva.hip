@@ -10,6 +10,12 @@
 //     the source sits in LDS; loads and stores run along T.
 //   k_hva_dual_step: per (b, f, t) Z again, the mask as a softmax over sources with the maximum
 //     subtracted, Yt = Z - mask Z and the relaxation of the dual variable.
+// MaskingADMMHVA (ref: ssspy/bss/hva.py:202-236 with ssspy/bss/admmbss.py:415-442) runs the same two
+// passes after the contraction and the filter step of admmbss.hip, on ADMM's operand
+// Z = relaxation W x + (1 - relaxation) auxiliary2 + dual2 (auxiliary2 is not read at relaxation 1):
+//   k_hva_cepstrum with the other Z former (HvaAdmmZ in the place of HvaPdsZ), one body;
+//   k_hva_aux_step: per (b, f, t) Z again, the same mask, auxiliary2 <- mask Z and
+//     dual2 <- Z - auxiliary2 in place, both from the registers that hold Z.
 // D by one of two routes (hva_plan):
 //   FFT    F - 1 = M a power of two: the even extension of length L = 2 M of TWO frames as the real
 //          and the imaginary part of one complex sequence; its DFT is D(frame a) + i D(frame b), both
@@ -96,13 +102,40 @@ __device__ __forceinline__ double hva_shrink(double nu, int mask_iter) {
   return sigma * nu;
 }
 
+// The two forms of Z the cepstral pass runs over: an entry of Z from y = (W x) of it and the entry's
+// offset in the state, off = b bstride + (n F + f) T + t.
+//   PDS:  Z = dual + W2 x
+struct HvaPdsZ {
+  const c128 *__restrict__ dual;
+  long long bstride;
+  __device__ __forceinline__ c128 at(c128 y, long long off) const { return cadd(dual[off], y); }
+};
+//   ADMM: Z = relax W x + (1 - relax) auxiliary2 + dual2, in the order of admm_form_z; mix == false
+//   (relaxation 1): auxiliary2 is not read
+struct HvaAdmmZ {
+  const c128 *__restrict__ aux2, *__restrict__ dual2;
+  long long bstride;
+  double relax;
+  bool mix;
+  __device__ __forceinline__ c128 at(c128 y, long long off) const {
+    if (mix) {
+      const double om = 1.0 - relax;
+      const c128 a = aux2[off];
+      y = cmake(relax * y.x + om * a.x, relax * y.y + om * a.y);
+    }
+    return cadd(y, dual2[off]);
+  }
+};
+
 // ---- the cepstral pass.  grid (N tiles, B), 512 threads, dynamic LDS hva_lds_bytes.  Workgroup
 // (n, tile, b) owns frames [tile TT, tile TT + TT) of source n; TT = 1 << log2tile.  Thread
 // (k0, tl) = (tid / TT, tid % TT) walks rows k0, k0 + 512 / TT, ... of column tl, so that the lanes
 // of a row read and write TT consecutive frames.  Columns past T hold zeros and are not stored.
+// ZForm: HvaPdsZ (W2 the filters of the dual step) or HvaAdmmZ (W2 the demixing filters).
+template <typename ZForm>
 __global__ __launch_bounds__(HVA_THREADS) void k_hva_cepstrum(
-    const c128 *__restrict__ X, const c128 *__restrict__ W2, const c128 *__restrict__ dual,
-    long long dual_bstride, const double *__restrict__ tab, double *__restrict__ varrho, int N, int F,
+    const c128 *__restrict__ X, const c128 *__restrict__ W2, ZForm zform,
+    const double *__restrict__ tab, double *__restrict__ varrho, int N, int F,
     int T, int floor_kind, double floor_eps, int mask_iter, int fft, int log2tile, int log2len) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int TT = 1 << log2tile;
@@ -118,7 +151,7 @@ __global__ __launch_bounds__(HVA_THREADS) void k_hva_cepstrum(
   const bool live = t < T;
   const long long FT = (long long)F * T;
   const c128 *__restrict__ Xb = X + (long long)b * N * FT;
-  const c128 *__restrict__ Db = dual + (long long)b * dual_bstride + (long long)n * FT;
+  const long long zoff = (long long)b * zform.bstride + (long long)n * FT;
 
   // zeta = log floor(|Z|) into rows 0 .. F - 1, the column sums on the way
   double part = 0.0;
@@ -128,7 +161,7 @@ __global__ __launch_bounds__(HVA_THREADS) void k_hva_cepstrum(
       const c128 *__restrict__ Wn = W2 + (((long long)b * F + f) * N + n) * N;
       c128 y = cmake(0.0, 0.0);
       for (int m = 0; m < N; ++m) cfma(y, Wn[m], Xb[((long long)m * F + f) * T + t]);
-      const c128 z = cadd(Db[(long long)f * T + t], y);
+      const c128 z = zform.at(y, zoff + (long long)f * T + t);
       zeta = log(apply_floor(hypot(z.x, z.y), floor_kind, floor_eps));
     }
     S[f * TT + tl] = zeta;
@@ -254,28 +287,103 @@ __global__ __launch_bounds__(PROX_THREADS) void k_hva_dual_step(
   for (int j = tid; j < T; j += PROX_THREADS) {
     c128 z[G];
     pds_form_z<G>(z, Xb, Db, Ws, N, FT, j);
-    double vr[G];
-    double mx = -HUGE_VAL;
-#pragma unroll
-    for (int n = 0; n < G; ++n) {
-      vr[n] = n < N ? Vb[n * FT + j] : 0.0;
-      if (n < N) mx = fmax(mx, vr[n]);  // (a NaN is skipped here and poisons the sum below)
-    }
-    double sum = 0.0;
-#pragma unroll
-    for (int n = 0; n < G; ++n)
-      if (n < N) sum += exp(2.0 * (vr[n] - mx));
-    const double den = pow(sum, gamma);
+    double mask[G];
+    hva_mask<G>(mask, Vb, N, FT, j, gamma);
 #pragma unroll
     for (int n = 0; n < G; ++n) {
       if (n < N) {
-        const double mask = exp(2.0 * gamma * (vr[n] - mx)) / den;
-        const c128 yt = cmake(z[n].x - mask * z[n].x, z[n].y - mask * z[n].y);
+        const c128 yt = cmake(z[n].x - mask[n] * z[n].x, z[n].y - mask[n] * z[n].y);
         const c128 d = Db[n * FT + j];
         Db[n * FT + j] = cmake(relax * yt.x + (1.0 - relax) * d.x, relax * yt.y + (1.0 - relax) * d.y);
       }
     }
   }
+}
+
+// ---- the masked auxiliary step of MaskingADMMHVA.  Grid and registers as k_hva_dual_step; a thread
+// reads the N entries of auxiliary2 / dual2 of its frame (admm_form_z) before it writes them.
+template <int G>
+__global__ __launch_bounds__(PROX_THREADS) void k_hva_aux_step(
+    const c128 *__restrict__ X, const c128 *__restrict__ W, c128 *aux2, c128 *dual2, long long bstride,
+    const double *__restrict__ varrho, int N, int F, int T, double gamma, double relax) {
+  __shared__ c128 Ws[G * G];
+  const int tid = threadIdx.x;
+  const int i = blockIdx.x, b = blockIdx.y;
+  const long long FT = (long long)F * T;
+  const bool mix = relax != 1.0;
+  const c128 *__restrict__ Xb = X + ((long long)b * N * F + i) * T;
+  const long long so = (long long)b * bstride + (long long)i * T;
+  c128 *Ab = aux2 + so, *Db = dual2 + so;
+  const double *__restrict__ Vb = varrho + ((long long)b * N * F + i) * T;  // row n at + n FT
+  if (tid < N * N) Ws[tid] = W[((long long)b * F + i) * (N * N) + tid];
+  __syncthreads();
+  for (int j = tid; j < T; j += PROX_THREADS) {
+    c128 z[G];
+    admm_form_z<G>(z, Xb, Ab, Db, Ws, N, FT, j, relax, mix);
+    double mask[G];
+    hva_mask<G>(mask, Vb, N, FT, j, gamma);
+#pragma unroll
+    for (int n = 0; n < G; ++n) {
+      if (n < N) {
+        const c128 v = cscale(z[n], mask[n]);
+        Ab[n * FT + j] = v;
+        Db[n * FT + j] = csub(z[n], v);
+      }
+    }
+  }
+}
+
+// ---- the checks and the launch of the cepstral pass over either form of Z; `present`: the pointers
+// of the form hold.  `word`: what the messages call the form's batch stride.
+template <typename ZForm>
+static int launch_cepstrum(const char *name, const char *word, bool present, const void *X,
+                           const void *W2, const ZForm &zform, const double *table, double *varrho,
+                           int B, int N, int F, int T, int floor_kind, double floor_eps, int mask_iter,
+                           int route, void *stream) {
+  char msg[160];
+  if (!(present && table && varrho && B > 0 && F > 0 && T > 0 && mask_iter >= 0)) {
+    std::snprintf(msg, sizeof(msg), "%s: bad argument", name);
+    return fail(SSSPY_ERR_BADARG, msg);
+  }
+  if (!(floor_kind >= SSSPY_FLOOR_NONE && floor_kind <= SSSPY_FLOOR_ADD)) {
+    std::snprintf(msg, sizeof(msg), "%s: bad flooring", name);
+    return fail(SSSPY_ERR_BADARG, msg);
+  }
+  if (!prox_shape_ok(B, N, F, T)) {
+    std::snprintf(msg, sizeof(msg), "%s: 1..16 sources, up to 65535 mixtures", name);
+    return fail(SSSPY_ERR_UNSUPPORTED, msg);
+  }
+  if (zform.bstride < (long long)N * F * T) {
+    std::snprintf(msg, sizeof(msg), "%s: bad %s stride", name, word);
+    return fail(SSSPY_ERR_BADARG, msg);
+  }
+  const HvaPlan plan = hva_plan(F, route);
+  if (!plan.ok) {
+    std::snprintf(msg, sizeof(msg),
+                  "%s: 2..8192 bins; the FFT route needs n_bins - 1 a power of two, n_bins <= 4097",
+                  name);
+    return fail(SSSPY_ERR_UNSUPPORTED, msg);
+  }
+  const bool fft = plan.route == SSSPY_HVA_ROUTE_FFT;
+  // no wider a tile than the frames there are (the FFT pairs frames: two at least)
+  int log2tile = ilog2_floor(plan.max_tile);
+  while (log2tile > (fft ? 1 : 0) && (1 << (log2tile - 1)) >= T) --log2tile;
+  const int tile = 1 << log2tile;
+  const long long blocks = ((long long)T + tile - 1) / tile * N;
+  if (blocks > 0x7fffffffll) {
+    std::snprintf(msg, sizeof(msg), "%s: too many frames", name);
+    return fail(SSSPY_ERR_UNSUPPORTED, msg);
+  }
+  const size_t lds = hva_lds_bytes(plan.rows, tile);
+  if (lds > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute((const void *)k_hva_cepstrum<ZForm>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return fail(SSSPY_ERR_HIP, hipGetErrorString(e));
+  }
+  hipLaunchKernelGGL((k_hva_cepstrum<ZForm>), dim3((unsigned)blocks, (unsigned)B), dim3(HVA_THREADS),
+                     lds, as_stream(stream), (const c128 *)X, (const c128 *)W2, zform, table, varrho, N,
+                     F, T, floor_kind, floor_eps, mask_iter, fft ? 1 : 0, log2tile, plan.log2len);
+  return check_launch("k_hva_cepstrum");
 }
 
 }  // namespace
@@ -304,36 +412,20 @@ int ssspy_hva_cepstrum(const void *X, const void *W2, const void *dual_q,
                        long long dual_batch_stride, const double *table, double *varrho, int B,
                        int N, int F, int T, int floor_kind, double floor_eps, int mask_iter,
                        int route, void *stream) {
-  SSSPY_REQUIRE(X && W2 && dual_q && table && varrho && B > 0 && F > 0 && T > 0 && mask_iter >= 0,
-                "hva_cepstrum: bad argument");
-  SSSPY_REQUIRE(floor_kind >= SSSPY_FLOOR_NONE && floor_kind <= SSSPY_FLOOR_ADD,
-                "hva_cepstrum: bad flooring");
-  if (!prox_shape_ok(B, N, F, T))
-    return fail(SSSPY_ERR_UNSUPPORTED, "hva_cepstrum: 1..16 sources, up to 65535 mixtures");
-  SSSPY_REQUIRE(dual_batch_stride >= (long long)N * F * T, "hva_cepstrum: bad dual stride");
-  const HvaPlan plan = hva_plan(F, route);
-  if (!plan.ok)
-    return fail(SSSPY_ERR_UNSUPPORTED,
-                "hva_cepstrum: 2..8192 bins; the FFT route needs n_bins - 1 a power of two, "
-                "n_bins <= 4097");
-  const bool fft = plan.route == SSSPY_HVA_ROUTE_FFT;
-  // no wider a tile than the frames there are (the FFT pairs frames: two at least)
-  int log2tile = ilog2_floor(plan.max_tile);
-  while (log2tile > (fft ? 1 : 0) && (1 << (log2tile - 1)) >= T) --log2tile;
-  const int tile = 1 << log2tile;
-  const long long blocks = ((long long)T + tile - 1) / tile * N;
-  if (blocks > 0x7fffffffll) return fail(SSSPY_ERR_UNSUPPORTED, "hva_cepstrum: too many frames");
-  const size_t lds = hva_lds_bytes(plan.rows, tile);
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void *)k_hva_cepstrum,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return fail(SSSPY_ERR_HIP, hipGetErrorString(e));
-  }
-  hipLaunchKernelGGL(k_hva_cepstrum, dim3((unsigned)blocks, (unsigned)B), dim3(HVA_THREADS), lds,
-                     as_stream(stream), (const c128 *)X, (const c128 *)W2, (const c128 *)dual_q,
-                     dual_batch_stride, table, varrho, N, F, T, floor_kind, floor_eps, mask_iter,
-                     fft ? 1 : 0, log2tile, plan.log2len);
-  return check_launch("k_hva_cepstrum");
+  const HvaPdsZ zform = {(const c128 *)dual_q, dual_batch_stride};
+  return launch_cepstrum("hva_cepstrum", "dual", X && W2 && dual_q, X, W2, zform, table, varrho, B, N,
+                         F, T, floor_kind, floor_eps, mask_iter, route, stream);
+}
+
+int ssspy_hva_admm_cepstrum(const void *X, const void *W, const void *aux2_q, const void *dual2_q,
+                            long long batch_stride, const double *table, double *varrho, int B, int N,
+                            int F, int T, double relaxation, int floor_kind, double floor_eps,
+                            int mask_iter, int route, void *stream) {
+  const HvaAdmmZ zform = {(const c128 *)aux2_q, (const c128 *)dual2_q, batch_stride, relaxation,
+                          relaxation != 1.0};
+  return launch_cepstrum("hva_admm_cepstrum", "batch", X && W && aux2_q && dual2_q && aux2_q != dual2_q,
+                         X, W, zform, table, varrho, B, N, F, T, floor_kind, floor_eps, mask_iter,
+                         route, stream);
 }
 
 int ssspy_hva_dual_step(const void *X, const void *W2, void *dual_q, long long dual_batch_stride,
@@ -347,6 +439,20 @@ int ssspy_hva_dual_step(const void *X, const void *W2, void *dual_q, long long d
                                               (const c128 *)W2, (c128 *)dual_q, dual_batch_stride,
                                               varrho, N, F, T, attenuation, relaxation));
   return check_launch("k_hva_dual_step");
+}
+
+int ssspy_hva_aux_step(const void *X, const void *W, void *aux2_q, void *dual2_q,
+                       long long batch_stride, const double *varrho, double attenuation,
+                       double relaxation, int B, int N, int F, int T, void *stream) {
+  const int rc = prox_check_args("hva_aux_step",
+                                 X && W && aux2_q && dual2_q && varrho && aux2_q != dual2_q, B, N, F, T,
+                                 {"batch", batch_stride});
+  if (rc != SSSPY_OK) return rc;
+  SSSPY_PROX_DISPATCH_G(N, hipLaunchKernelGGL((k_hva_aux_step<GG>), dim3((unsigned)F, (unsigned)B),
+                                              dim3(PROX_THREADS), 0, as_stream(stream), (const c128 *)X,
+                                              (const c128 *)W, (c128 *)aux2_q, (c128 *)dual2_q,
+                                              batch_stride, varrho, N, F, T, attenuation, relaxation));
+  return check_launch("k_hva_aux_step");
 }
 
 }  // extern "C"

@@ -1,9 +1,10 @@
 // What the spectrogram-sized passes of the proximal separators share (pdsbss.hip, admmbss.hip,
 // hva.hip): the contraction R_i = d_i X_i^H per bin with the family's operand, Z = dual_q + W2 x of one
-// (bin, frame), the shrinkage factor, the chunks of the norm pass over bins, the source-count dispatches
-// and the argument check of the entry points.  The norm pass, the point step and ADMMBSS's Z former stay
-// in the units: cut into shared templates or helpers they need more registers than the kernels they
-// would replace ("PDSBSS").
+// (bin, frame) and ADMMBSS's Z = relax W x + (1 - relax) auxiliary2_q + dual2_q of it, the HVA mask of
+// one (bin, frame), the shrinkage factor, the chunks of the norm pass over bins, the source-count
+// dispatches and the argument check of the entry points.  The norm pass and the point step stay in the
+// units: cut into shared templates or helpers they need more registers than the kernels they would
+// replace ("PDSBSS").
 // fp64 / complex128, no atomics, every sum in a fixed order: two runs give the same bits.
 #pragma once
 
@@ -37,6 +38,56 @@ __device__ __forceinline__ void pds_form_z(c128 (&z)[G], const c128 *__restrict_
       z[n] = cadd(Db[n * FT + j], y);
     }
   }
+}
+
+// z_n = relax (W x)_n + (1 - relax) a_n + d_n for the N rows of one (bin, frame); Wn: row-major N x N.
+// mix == false (relaxation 1): a is not read, z_n = (W x)_n + d_n.
+template <int G, typename WPtr>
+__device__ __forceinline__ void admm_form_z(c128 (&z)[G], const c128 *__restrict__ Xb, const c128 *Ab,
+                                            const c128 *Db, WPtr Wn, int N, long long FT, int j,
+                                            double relax, bool mix) {
+  c128 x[G];
+#pragma unroll
+  for (int m = 0; m < G; ++m) x[m] = m < N ? Xb[m * FT + j] : cmake(0.0, 0.0);
+  const double om = 1.0 - relax;
+#pragma unroll
+  for (int n = 0; n < G; ++n) {
+    z[n] = cmake(0.0, 0.0);
+    if (n < N) {
+      c128 y = cmake(0.0, 0.0);
+#pragma unroll
+      for (int m = 0; m < G; ++m)
+        if (m < N) cfma(y, Wn[n * N + m], x[m]);
+      if (mix) {
+        const c128 a = Ab[n * FT + j];
+        y = cmake(relax * y.x + om * a.x, relax * y.y + om * a.y);
+      }
+      z[n] = cadd(y, Db[n * FT + j]);
+    }
+  }
+}
+
+// the HVA mask of the N sources of one (bin, frame) from varrho (row n at Vb + n FT): the softmax of
+// 2 varrho over sources with the maximum subtracted, to the power gamma,
+// mask_n = exp(2 gamma (varrho_n - max)) / (sum_n' exp(2 (varrho_n' - max)))^gamma
+// (ref: ssspy/bss/hva.py:112-115, :232-234).  A NaN in any source's varrho makes every mask NaN.
+template <int G>
+__device__ __forceinline__ void hva_mask(double (&mask)[G], const double *__restrict__ Vb, int N,
+                                         long long FT, int j, double gamma) {
+  double vr[G];
+  double mx = -HUGE_VAL;
+#pragma unroll
+  for (int n = 0; n < G; ++n) {
+    vr[n] = n < N ? Vb[n * FT + j] : 0.0;
+    if (n < N) mx = fmax(mx, vr[n]);  // (a NaN is skipped here and poisons the sum below)
+  }
+  double sum = 0.0;
+#pragma unroll
+  for (int n = 0; n < G; ++n)
+    if (n < N) sum += exp(2.0 * (vr[n] - mx));
+  const double den = pow(sum, gamma);
+#pragma unroll
+  for (int n = 0; n < G; ++n) mask[n] = n < N ? exp(2.0 * gamma * (vr[n] - mx)) / den : 0.0;
 }
 
 // ---- R[b,i,n,m] = sum_j d[b,n,i,j] conj(X[b,m,i,j]); the operand d = op.at(off, j, Q, N FT) with off
