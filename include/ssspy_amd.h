@@ -284,6 +284,12 @@ int ssspy_demix_from_covariance(const void *YX, const void *XX, void *W, int B, 
  * replaces: np.linalg.slogdet at ssspy/bss/ilrma.py:534, iva.py:234, mnmf.py:1274. */
 int ssspy_sum_logdet(const void *W, double *out, int B, int F, int N, void *stream);
 
+/* out[i] = log|det W_i| of n matrices (n, N, N), 1 <= N <= 16: LU with partial pivoting, a lane per
+ * matrix; -inf for an exactly singular matrix, as numpy.linalg.slogdet.  The per-bin values behind
+ * compute_logdet (ssspy/bss/iva.py:224-236, ilrma.py:524-536) for a filter that is on the device.
+ * (Added at SSSPY_ABI_VERSION 11 without a bump: no existing argument list changed.) */
+int ssspy_logdet(const void *W, double *out, long long n, int N, void *stream);
+
 /* ------------------------------------------------------------------ batched small linear algebra */
 /* Device counterparts of ssspy.linalg / ssspy.special.psd: `n` independent matrices, one per lane.
  * Sizes up to 8 x 8 are instantiated per size; 9 x 9 .. SSSPY_RT_MAX_SOURCES (16) take the size at
@@ -1413,6 +1419,18 @@ int ssspy_ipsdta_vcd(void *W, const void *weighted_covariance, int B, int F, int
 int ssspy_matmul3(const void *A, const void *Bm, const void *C, void *out, long long n, int L,
                   void *stream);
 
+/* The PSDTF handed out: out (S, T, n_part_blocks, L, L) c128 = to_psd(sum_k v[s, k, t] T[s, k, c])
+ * with the floor (floor_kind, floor_eps) on the eigenvalues; exactly Hermitian.  S counts the leading
+ * (mixture, source) pairs; activation (S, K, T) f64; basis (S, K, n_part_blocks, L, L) c128, or with
+ * basis_last != 0 the reference's other layout (S, n_part_blocks, L, L, K).  1 <= L <= 16 (above 8:
+ * the full-matrix PSDTF of IPSDTABase.reconstruct_psdtf, n_part_blocks == 1), 1 <= K <= 32.
+ * A lane per matrix, the sum over k in the order of k.
+ * replaces: ssspy/bss/ipsdta.py:260-300 (reconstruct_psdtf), :584-664.
+ * (Added at SSSPY_ABI_VERSION 11 without a bump: no existing argument list changed.) */
+int ssspy_ipsdta_reconstruct(const void *basis, const double *activation, void *out, long long S,
+                             int K, int T, int n_part_blocks, int L, int basis_last, int floor_kind,
+                             double floor_eps, void *stream);
+
 /* ------------------------------------------------------------------ permutation alignment
  * The two solvers of ssspy/algorithm/permutation_alignment.py, batched and device-resident
  * (csrc/permutation.hip), with the decisions of the host solvers of this package: the first
@@ -1478,6 +1496,25 @@ int ssspy_permute_sources(const void *src, void *dst, const int *perm, int B, in
 /* out (B, N, F, T) = |posterior X[:, reference_id]|: the amplitude targets of CACGMM's alignment */
 int ssspy_permutation_amplitude(const double *posterior, const void *X, double *out, int B, int N,
                                 int M, int F, int T, int reference_id, void *stream);
+
+/* ------------------------------------------------------------------ special functions, quadratic forms
+ * The device forms of ssspy.special.softmax / logsumexp and ssspy.linalg.quadratic for tensors that
+ * are on the device already (csrc/special.hip).  A float64 tensor reduced over one axis is
+ * addressed as (outer, len, inner), contiguous, the reduced axis in the middle: inner == 1 when it
+ * is the last axis, otherwise the axis is walked by its stride.  The maximum of a row is subtracted
+ * before exp; a wave owns a row, lane l sums elements l, l + 64, ... in order and the 64 partial sums
+ * meet in a fixed butterfly: two runs give the same bits.
+ * (Added at SSSPY_ABI_VERSION 11 without a bump: no existing argument list changed.) */
+
+/* out (outer, len, inner) = exp(x - max) / sum exp(x - max).  replaces: ssspy/special/softmax.py:4-36 */
+int ssspy_softmax(const double *X, double *out, long long outer, int len, long long inner,
+                  void *stream);
+/* out (outer, inner) = log sum exp(x - max) + max.  replaces: ssspy/special/logsumexp.py:4-40 */
+int ssspy_logsumexp(const double *X, double *out, long long outer, int len, long long inner,
+                    void *stream);
+/* out[i] = x_i^H A_i x_i.  X (n, N), A (n, N, N), out (n) complex128, 1 <= N <= 16; a lane per form.
+ * replaces: ssspy/linalg/quadratic.py:4-25. */
+int ssspy_quadratic(const void *X, const void *A, void *out, long long n, int N, void *stream);
 
 /* ------------------------------------------------------------------ STFT / ISTFT
  * The transforms the reference's workflow takes from SciPy either side of a separator

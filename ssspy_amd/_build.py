@@ -55,6 +55,7 @@ def _units():
         ("ipsdta.hip", "ipsdta.o", []),
         ("cacgmm.hip", "cacgmm.o", []),
         ("permutation.hip", "permutation.o", []),
+        ("special.hip", "special.o", []),
         ("iss_fused.hip", "iss_fused.o", []),
         ("linalg_kernels.hip", "linalg_kernels.o", []),
         ("pairwise_kernels.hip", "pairwise_kernels.o", []),

@@ -105,6 +105,7 @@ PROTOTYPES = {
     "ssspy_projection_back_scale": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p]),
     "ssspy_demix_from_covariance": (_i, [_p, _p, _p, _i, _i, _i, _p, _p]),
     "ssspy_sum_logdet": (_i, [_p, _p, _i, _i, _i, _p]),
+    "ssspy_logdet": (_i, [_p, _p, _q, _i, _p]),
     "ssspy_solve": (_i, [_p, _p, _p, _q, _i, _i, _p, _p]),
     "ssspy_inv2": (_i, [_p, _p, _q, _p]),
     "ssspy_eigh": (_i, [_p, _p, _p, _q, _i, _p]),
@@ -194,6 +195,10 @@ PROTOTYPES = {
     "ssspy_ipsdta_normalize": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "ssspy_ipsdta_vcd": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _d, _p, _p]),
     "ssspy_matmul3": (_i, [_p, _p, _p, _p, _q, _i, _p]),
+    "ssspy_ipsdta_reconstruct": (_i, [_p, _p, _p, _q, _i, _i, _i, _i, _i, _i, _d, _p]),
+    "ssspy_softmax": (_i, [_p, _p, _q, _i, _q, _p]),
+    "ssspy_logsumexp": (_i, [_p, _p, _q, _i, _q, _p]),
+    "ssspy_quadratic": (_i, [_p, _p, _p, _q, _i, _p]),
     "ssspy_cacgmm_unit_input": (_i, [_p, _p, _i, _i, _i, _i, _i, _d, _p]),
     "ssspy_cacgmm_prepare": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p]),
     "ssspy_cacgmm_frame_pass": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _d, _p, _p, _p, _p, _p,

@@ -411,6 +411,15 @@ def sum_logdet(W, out=None):
     return out
 
 
+def logdet(W):
+    """log|det W| of every matrix of a device stack (..., N, N) c128 -> f64 (...); -inf where singular."""
+    N = W.shape[-1]
+    out = dv.empty(tuple(W.shape[:-2]), dv.f64, W.device)
+    if out.numel():
+        _lib.check(_L().ssspy_logdet(ptr(W), ptr(out), out.numel(), N, _st()), "logdet")
+    return out
+
+
 # ----------------------------------------------------------------------------- ILRMA
 def ilrma_workspace(B, N, F, T, K, dev):
     return _workspace(_L().ssspy_ilrma_workspace_bytes(B, N, F, T, K), dev)
@@ -1664,6 +1673,24 @@ def ipsdta_vcd(W, weighted_covariance, first_bin, threshold, info=None):
     return W
 
 
+def ipsdta_reconstruct(basis, activation, flooring, basis_last=False):
+    """to_psd(sum_k v T) (..., T, C, L, L) from a device basis (..., K, C, L, L) -- with basis_last
+    (..., C, L, L, K) -- and activation (..., K, T); flooring a device floor (kind, eps)."""
+    if basis_last:
+        C, L, K = basis.shape[-4], basis.shape[-3], basis.shape[-1]
+    else:
+        K, C, L = basis.shape[-4], basis.shape[-3], basis.shape[-1]
+    lead = tuple(activation.shape[:-2])
+    T = activation.shape[-1]
+    assert activation.shape[-2] == K and basis.numel() == activation.numel() // T * C * L * L
+    out = dv.empty(lead + (T, C, L, L), dv.c128, basis.device)
+    if out.numel():
+        _lib.check(_L().ssspy_ipsdta_reconstruct(
+            ptr(basis), ptr(activation), ptr(out), activation.numel() // (K * T), K, T, C, L,
+            int(bool(basis_last)), int(flooring[0]), float(flooring[1]), _st()), "ipsdta_reconstruct")
+    return out
+
+
 def matmul3(A, Bm, C):
     """(A B) C for stacks (..., L, L) of small matrices on the device."""
     L = A.shape[-1]
@@ -1695,4 +1722,43 @@ def gmeanmh_dev(A, Bm, type=1):
     out = dv.empty(tuple(A.shape), dv.c128, A.device)
     _lib.check(_L().ssspy_gmeanmh(ptr(A), ptr(Bm), ptr(out), A.numel() // (L * L), L, type, _st()),
                "gmeanmh")
+    return out
+
+
+# ---- softmax, logsumexp, quadratic forms of device tensors (csrc/special.hip).  The reduced axis of
+# a contiguous tensor is addressed as (outer, len, inner): nothing is transposed.
+def _axis_split(X, axis):
+    outer = 1
+    for s in X.shape[:axis]:
+        outer *= s
+    inner = 1
+    for s in X.shape[axis + 1:]:
+        inner *= s
+    return outer, X.shape[axis], inner
+
+
+def softmax_dev(X, axis):
+    """softmax over ``axis`` (normalised, >= 0) of a contiguous f64 device tensor."""
+    outer, n, inner = _axis_split(X, axis)
+    out = dv.empty(tuple(X.shape), dv.f64, X.device)
+    if out.numel():
+        _lib.check(_L().ssspy_softmax(ptr(X), ptr(out), outer, n, inner, _st()), "softmax")
+    return out
+
+
+def logsumexp_dev(X, axis):
+    """log-sum-exp over ``axis`` of a contiguous f64 device tensor; that axis is dropped."""
+    outer, n, inner = _axis_split(X, axis)
+    out = dv.empty(tuple(X.shape[:axis]) + tuple(X.shape[axis + 1:]), dv.f64, X.device)
+    if out.numel():
+        _lib.check(_L().ssspy_logsumexp(ptr(X), ptr(out), outer, n, inner, _st()), "logsumexp")
+    return out
+
+
+def quadratic_dev(X, A):
+    """x^H A x of contiguous c128 device stacks X (..., n), A (..., n, n) -> c128 (...)."""
+    n = X.shape[-1]
+    out = dv.empty(tuple(X.shape[:-1]), dv.c128, X.device)
+    if out.numel():
+        _lib.check(_L().ssspy_quadratic(ptr(X), ptr(A), ptr(out), out.numel(), n, _st()), "quadratic")
     return out

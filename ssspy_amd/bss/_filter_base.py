@@ -8,7 +8,7 @@ the ISS state are the same for both and live here.
 import numpy as np
 
 from .. import _device as dv
-from .. import _ops, _routes
+from .. import _lib, _ops, _routes
 from ..utils.flooring import choose_flooring_fn, device_flooring
 from ..utils.select_pair import resolve_pairs
 from ._device_state import DeviceStateMixin, Synced
@@ -21,6 +21,25 @@ _ISS2 = ("ISS2",)
 _IPA = ("IPA",)
 _PROJECTION_BACK = ("projection_back",)
 _MDP = ("minimal_distortion_principle",)
+
+
+def filter_logdet(demix_filter):
+    """log|det W_i| per bin, the ``compute_logdet`` of IVABase and ILRMABase (ref:
+    ssspy/bss/iva.py:224-236, ilrma.py:524-536).  A NumPy argument is the reference's own line,
+    ``numpy.linalg.slogdet`` on the host.  A complex128 torch tensor on the device, (n_bins,
+    n_sources, n_sources) or with a leading mixture axis, goes through one LU per lane there and a
+    float64 tensor of the leading shape comes back (``-inf`` for a singular filter)."""
+    if type(demix_filter).__module__.split(".")[0] != "torch":
+        return np.linalg.slogdet(demix_filter)[1]
+    W = demix_filter
+    limit = _lib.RT_MAX_SOURCES
+    if (not W.is_cuda or W.dtype != dv.c128 or W.ndim not in (3, 4) or W.shape[-1] != W.shape[-2]
+            or not 1 <= W.shape[-1] <= limit):
+        raise NotImplementedError(
+            "compute_logdet on the device takes a complex128 tensor (n_bins, n, n) or (n_mixtures, "
+            "n_bins, n, n) on a HIP device with n in 1..{}, got {} {} on {} (convert to NumPy for "
+            "the host form)".format(limit, W.dtype, tuple(W.shape), W.device))
+    return _ops.logdet(W.contiguous())
 
 
 class DemixingFilterBase(DeviceStateMixin, IterativeMethodBase):

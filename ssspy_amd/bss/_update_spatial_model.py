@@ -5,7 +5,7 @@ functions on C-contiguous arrays.  Inputs may carry an extra leading batch axis.
 """
 
 import functools
-from typing import Callable, Optional
+from typing import Callable, Optional, Tuple
 
 import numpy as np
 
@@ -15,6 +15,9 @@ from ..special.flooring import max_flooring
 from ..utils.flooring import device_flooring
 from ..utils.select_pair import resolve_pairs, sequential_pair_selector
 from ._device_state import newton_words
+
+__all__ = ["update_by_ip1", "update_by_iss1", "update_by_ip2", "update_by_iss2",
+           "update_by_ip2_one_pair", "update_by_ipa", "update_by_block_decomposition_vcd"]
 
 EPS = 1e-10
 _DEFAULT_FLOOR = functools.partial(max_flooring, eps=EPS)
@@ -144,6 +147,49 @@ def update_by_iss2(
     out = dv.to_host(_ops.separate(Y, G))[0]
     _lib.raise_if_singular(int(info.item()), "update_by_iss2")
     return out
+
+
+def update_by_ip2_one_pair(
+    demix_filter: np.ndarray,
+    weighted_covariance_pair: np.ndarray,
+    pair: Tuple[int],
+    flooring_fn: Optional[Callable[[np.ndarray], np.ndarray]] = _DEFAULT_FLOOR,
+) -> np.ndarray:
+    """The two rows pairwise iterative projection gives one pair of sources (ref: :317-395).
+
+    Args:
+        demix_filter: (n_bins, n_sources, n_channels) complex, 2 to 16 sources; left as it is.
+        weighted_covariance_pair: (n_bins, 2, n_channels, n_channels) complex: the covariances of
+            sources ``pair[0]`` and ``pair[1]``, nothing else goes to the device.
+        pair: the two distinct source indices ``(m, n)``.
+        flooring_fn: as for ``update_by_ip2``.
+
+    Returns:
+        (n_bins, 2, n_channels): the new rows ``m`` and ``n``, with the eigenvector phases of
+        ``update_by_ip2`` (the same kernel runs with that single pair).
+
+    Raises:
+        numpy.linalg.LinAlgError: if a bin's system ``W U`` is singular.
+    """
+    floor = device_flooring(flooring_fn, what="update_by_ip2_one_pair", allow_host=True)
+    W = np.asarray(demix_filter)
+    U = np.asarray(weighted_covariance_pair)
+    F, N, M = W.shape
+    m, n = (int(v) for v in pair)
+    if N != M or not 2 <= N <= _lib.RT_MAX_SOURCES:
+        raise NotImplementedError("update_by_ip2_one_pair takes 2 to {} sources (square filters), got "
+                                  "{} x {}.".format(_lib.RT_MAX_SOURCES, N, M))
+    if U.shape != (F, 2, N, N):
+        raise ValueError("weighted_covariance_pair must be (n_bins, 2, n_channels, n_channels) = {}, "
+                         "got {}.".format((F, 2, N, N), U.shape))
+    if not (0 <= m < N and 0 <= n < N) or m == n:
+        raise ValueError("pair must name two distinct sources in [0, {}), got {}.".format(N, pair))
+    dW = dv.to_device(W[None], dtype=np.complex128)
+    dU = dv.to_device(U[None], dtype=np.complex128)
+    info = dv.zeros((1,), dv.i32)
+    _ops.update_by_ip2(dW, dU, [(m, n)], floor, info, pair_only=True)
+    _lib.raise_if_singular(int(info.item()), "update_by_ip2_one_pair")
+    return dv.to_host(dW[0][:, [m, n], :])
 
 
 def update_by_ipa(

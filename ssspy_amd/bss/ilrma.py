@@ -25,7 +25,7 @@ from ..special.flooring import identity, max_flooring
 from ..utils.flooring import choose_flooring_fn, device_flooring, host_floor, require_device_floor
 from ..utils.select_pair import resolve_pairs, sequential_pair_selector
 from ._device_state import LossShares, Synced
-from ._filter_base import _IP1, _IP2, _IPA, _ISS1, _ISS2, DemixingFilterBase
+from ._filter_base import _IP1, _IP2, _IPA, _ISS1, _ISS2, DemixingFilterBase, filter_logdet
 from .base import IterativeMethodBase
 
 __all__ = ["GaussILRMA", "TILRMA", "GGDILRMA"]
@@ -128,6 +128,11 @@ class ILRMABase(DemixingFilterBase):
         W = dv.to_device(demix_filter if batched else demix_filter[None], dtype=np.complex128)
         Y = dv.to_host(_ops.separate(X, W))
         return Y if batched else Y[0]
+
+    def compute_logdet(self, demix_filter: np.ndarray) -> np.ndarray:
+        """log|det W_i| per bin (ref: ssspy/bss/ilrma.py:524-536): NumPy on the host, a complex128
+        device tensor on the device (see ``filter_logdet``)."""
+        return filter_logdet(demix_filter)
 
     def reconstruct_nmf(self, basis, activation, latent=None) -> np.ndarray:
         """R = T V (ref: ssspy/bss/ilrma.py:297-327); host-side convenience, not on the hot path."""

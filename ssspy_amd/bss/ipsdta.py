@@ -87,6 +87,66 @@ class IPSDTABase(DemixingFilterBase):
         Y = dv.to_host(_ops.separate(X, W))
         return Y if batched else Y[0]
 
+    def _reconstruct(self, basis, activation, axis1: int, axis2: int) -> np.ndarray:
+        """to_psd(sum_k v_k T_k) for a basis (..., K, C, L, L) -- (..., C, L, L, K) when the matrix
+        axes are the second and third from the end -- and an activation (..., K, T): (..., T, C, L, L).
+        The floor on the eigenvalues is the instance's.  Matrices up to 16 x 16 with up to
+        ``IPSDTA_MAX_BASIS`` bases and a built-in floor go through one kernel, a lane per matrix;
+        anything else is summed on the host and handed to ``ssspy_amd.special.to_psd``."""
+        T, V = np.asarray(basis), np.asarray(activation)
+        nd = T.ndim
+        axis1 = nd + axis1 if axis1 < 0 else axis1
+        axis2 = nd + axis2 if axis2 < 0 else axis2
+        assert (axis1 == nd - 3 and axis2 == nd - 2) or (axis1 == nd - 2 and axis2 == nd - 1)
+        basis_last = axis1 == nd - 3
+        floor = device_flooring(self.flooring_fn, allow_host=True)
+        L, K = T.shape[axis1], V.shape[-2]
+        if (host_floor(floor) is None and L <= _lib.RT_MAX_SOURCES
+                and 1 <= K <= _lib.IPSDTA_MAX_BASIS):
+            R = _ops.ipsdta_reconstruct(dv.to_device(T, dtype=np.complex128),
+                                        dv.to_device(V, dtype=np.float64), floor, basis_last)
+            return dv.to_host(R)
+        from ..special.psd import to_psd
+
+        if basis_last:
+            T = np.moveaxis(T, -1, -4)
+        na = np.newaxis
+        R = np.sum(T[..., :, na, :, :, :] * V[..., :, :, na, na, na], axis=-5)
+        return to_psd(R, flooring_fn=self.flooring_fn)
+
+    def reconstruct_psdtf(self, basis: np.ndarray, activation: np.ndarray, axis1: int = -2,
+                          axis2: int = -1) -> np.ndarray:
+        """R_nt = to_psd(sum_k v_nkt T_nk) (ref: ssspy/bss/ipsdta.py:260-300).
+
+        Args:
+            basis: (n_sources, n_basis, n_bins, n_bins), or (n_sources, n_bins, n_bins, n_basis)
+                with ``axis1=-3, axis2=-2`` (``1, 2``).
+            activation: (n_sources, n_basis, n_frames).
+
+        Returns:
+            (n_sources, n_frames, n_bins, n_bins), exactly Hermitian.  Up to 16 bins the block kernel
+            of ``reconstruct_block_decomposition_psdtf`` runs with one block; above, the sum is formed
+            on the host and ``ssspy_amd.special.to_psd`` floors it, with the sizes that function takes.
+        """
+        T = np.asarray(basis)
+        nd = T.ndim
+        a1 = nd + axis1 if axis1 < 0 else axis1
+        a2 = nd + axis2 if axis2 < 0 else axis2
+        assert (a1 == 1 and a2 == 2) or (a1 == 2 and a2 == 3)
+        # one block that spans every bin: (n_sources, n_basis, 1, n_bins, n_bins)
+        T = T[:, np.newaxis] if a1 == 1 else T[:, :, np.newaxis]
+        return self._reconstruct(T, activation, a1 + 1, a2 + 1)[:, :, 0]
+
+    def normalize_psdtf(self) -> None:
+        """T / tr T, V tr T per (source, basis) (ref: ssspy/bss/ipsdta.py:306-317).  Host only: a
+        pass over the n_sources x n_basis matrices, through the ``basis`` and ``activation``
+        attributes."""
+        assert self.source_normalization, "Set source_normalization."
+        T, V = self.basis, self.activation
+        trace = np.trace(T, axis1=-2, axis2=-1).real
+        self.basis = T / trace[:, :, np.newaxis, np.newaxis]
+        self.activation = V * trace[:, :, np.newaxis]
+
     def update_once(self) -> None:
         raise NotImplementedError("Implement 'update_once' method.")
 
@@ -268,6 +328,28 @@ class BlockDecompositionIPSDTABase(IPSDTABase):
             self.activation = np.array(self.activation, dtype=np.float64, copy=True)
         if self.source_normalization:
             self.normalize_block_decomposition_psdtf()
+
+    def reconstruct_block_decomposition_psdtf(self, basis, activation, axis1: int = -2,
+                                              axis2: int = -1):
+        """R_ntc = to_psd(sum_k v_nkt T_nkc) per block (ref: ssspy/bss/ipsdta.py:584-664): the
+        matrices the frame passes form and keep to themselves, handed out.
+
+        Args:
+            basis: (n_sources, n_basis, n_blocks, n_neighbors, n_neighbors), or (n_sources,
+                n_blocks, n_neighbors, n_neighbors, n_basis) with ``axis1=-3, axis2=-2``; or the
+                pair ``(basis_low, basis_high)`` when ``n_bins % n_blocks > 0``.
+            activation: (n_sources, n_basis, n_frames).
+
+        Returns:
+            (n_sources, n_frames, n_blocks, n_neighbors, n_neighbors), exactly Hermitian; a pair for
+            a pair.
+        """
+        if type(basis) is tuple:
+            assert self.n_remains > 0, "n_remains is expected to be positive."
+            T_low, T_high = basis
+            return (self._reconstruct(T_low, activation, axis1, axis2),
+                    self._reconstruct(T_high, activation, axis1, axis2))
+        return self._reconstruct(basis, activation, axis1, axis2)
 
     def normalize_block_decomposition_psdtf(self, axis1: int = -2, axis2: int = -1) -> None:
         """T / tr, V tr with the traces summed over both partitions (ref: ipsdta.py:666-697)."""

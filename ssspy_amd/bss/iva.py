@@ -37,7 +37,7 @@ from ..special.flooring import identity, max_flooring
 from ..utils.flooring import choose_flooring_fn, device_flooring, host_floor, require_device_floor
 from ..utils.select_pair import resolve_pairs, sequential_pair_selector
 from ._device_state import LossShares, Synced
-from ._filter_base import _IP1, _IP2, _IPA, _ISS1, _ISS2, DemixingFilterBase
+from ._filter_base import _IP1, _IP2, _IPA, _ISS1, _ISS2, DemixingFilterBase, filter_logdet
 from .admmbss import ADMMBSS
 from .base import IterativeMethodBase
 from .pdsbss import PDSBSS
@@ -109,6 +109,11 @@ class IVABase(DemixingFilterBase):
         W = dv.to_device(demix_filter if batched else demix_filter[None], dtype=np.complex128)
         Y = dv.to_host(_ops.separate(X, W))
         return Y if batched else Y[0]
+
+    def compute_logdet(self, demix_filter: np.ndarray) -> np.ndarray:
+        """log|det W_i| per bin (ref: ssspy/bss/iva.py:224-236): NumPy on the host, a complex128
+        device tensor on the device (see ``filter_logdet``)."""
+        return filter_logdet(demix_filter)
 
 
 class AuxIVABase(IVABase):

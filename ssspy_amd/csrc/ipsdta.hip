@@ -500,6 +500,51 @@ __global__ __launch_bounds__(64) void k_matmul3(const c128 *__restrict__ A, cons
   }
 }
 
+// R[s, t, c] = to_psd(sum_k v[s, k, t] T[s, k, c]) handed out: (S, T, Cn, L, L), a lane per matrix
+// (c fastest).  The sum over k stays in the lane, in the order of k; then the per-lane Hermitian
+// to_psd (hermitian.hpp) at every matrix -- no Cholesky shortcut: what leaves is what the floor made.
+// basis_last == 0: basis (S, K, Cn, L, L); != 0: (S, Cn, L, L, K), the reference's other layout.
+// A lane past the end works on the last matrix and stores nothing (the Jacobi sweeps end on a wave
+// vote).  D: Fixed<L> to 4 x 4, Fixed<L, true> to 8 x 8, Runtime above (the full-matrix PSDTF).
+template <class D>
+__global__ __launch_bounds__(64) void k_psdtf_reconstruct(D d, const c128 *__restrict__ basis,
+                                                          const double *__restrict__ V, c128 *out,
+                                                          long long n, int K, int T, int Cn,
+                                                          int basis_last, int floor_kind,
+                                                          double eps) {
+  constexpr int CC = D::cap * D::cap;
+  const int L = d.n(), E = L * L;
+  const long long lane = (long long)blockIdx.x * 64 + threadIdx.x;
+  const bool live = lane < n;
+  const long long idx = live ? lane : n - 1;
+  const int c = (int)(idx % Cn);
+  const int t = (int)((idx / Cn) % T);
+  const long long s = idx / ((long long)Cn * T);
+  const double *v = V + s * K * T + t;  // + k * T
+  // element e of T_k: basis_last == 0 at Tb[k * k_stride + e], else at Tb[e * K + k]
+  const c128 *Tb = basis_last ? basis + (s * Cn + c) * E * K : basis + (s * K * Cn + c) * E;
+  const long long k_stride = basis_last ? 1 : (long long)Cn * E;
+  const long long e_stride = basis_last ? K : 1;
+  c128 R[CC], P[CC];
+  double lam[D::cap];
+#pragma unroll D::unroll
+  for (int e = 0; e < E; ++e) R[e] = cmake(0.0, 0.0);
+  for (int k = 0; k < K; ++k) {
+    const double vk = v[(long long)k * T];
+#pragma unroll D::unroll
+    for (int e = 0; e < E; ++e) {
+      const c128 z = Tb[k * k_stride + e * e_stride];
+      R[e].x = fma(vk, z.x, R[e].x);
+      R[e].y = fma(vk, z.y, R[e].y);
+    }
+  }
+  psd_eigen(d, R, P, lam, floor_kind, eps);
+  rebuild(d, P, lam, R);
+  if (!live) return;
+#pragma unroll D::unroll
+  for (int e = 0; e < E; ++e) out[idx * E + e] = R[e];
+}
+
 int check_sizes(int N, int L, int K) {
   if (N < 2 || N > 8) return fail(SSSPY_ERR_UNSUPPORTED, "IPSDTA takes 2 to 8 sources");
   if (L < 1 || L > IPSDTA_MAX_L)
@@ -598,6 +643,44 @@ int ssspy_ipsdta_vcd(void *W, const void *weighted_covariance, int B, int F, int
                                    (c128 *)W, (const c128 *)weighted_covariance, B, F,
                                    n_part_blocks, L, first_bin, threshold, info));
   return check_launch("k_ipsdta_vcd");
+}
+
+int ssspy_ipsdta_reconstruct(const void *basis, const double *activation, void *out, long long S,
+                             int K, int T, int n_part_blocks, int L, int basis_last, int floor_kind,
+                             double floor_eps, void *stream) {
+  SSSPY_REQUIRE(basis && activation && out, "ipsdta_reconstruct: null pointer");
+  SSSPY_REQUIRE(S > 0 && T > 0 && n_part_blocks > 0, "ipsdta_reconstruct: empty problem");
+  SSSPY_REQUIRE(floor_kind >= SSSPY_FLOOR_NONE && floor_kind <= SSSPY_FLOOR_ADD,
+                "ipsdta_reconstruct: unknown floor");
+  if (L < 1 || L > SSSPY_RT_MAX_SOURCES)
+    return fail(SSSPY_ERR_UNSUPPORTED, "ipsdta_reconstruct takes matrices of 1 x 1 to 16 x 16");
+  if (K < 1 || K > IPSDTA_MAX_K)
+    return fail(SSSPY_ERR_UNSUPPORTED, "ipsdta_reconstruct takes 1 to 32 bases");
+  SSSPY_REQUIRE(S <= (1LL << 36) / T / n_part_blocks, "ipsdta_reconstruct: too many matrices");
+  const long long n = S * T * n_part_blocks;
+  const dim3 grid((unsigned)((n + 63) / 64)), block(64);
+  const hipStream_t st = as_stream(stream);
+#define SSSPY_RECONSTRUCT(DESC, VALUE)                                                          \
+  hipLaunchKernelGGL((k_psdtf_reconstruct<DESC>), grid, block, 0, st, VALUE, (const c128 *)basis, \
+                     activation, (c128 *)out, n, K, T, n_part_blocks, basis_last ? 1 : 0,      \
+                     floor_kind, floor_eps)
+  using Rolled5 = Fixed<5, true>;
+  using Rolled6 = Fixed<6, true>;
+  using Rolled7 = Fixed<7, true>;
+  using Rolled8 = Fixed<8, true>;
+  switch (L) {
+    case 1: SSSPY_RECONSTRUCT(Fixed<1>, Fixed<1>{}); break;
+    case 2: SSSPY_RECONSTRUCT(Fixed<2>, Fixed<2>{}); break;
+    case 3: SSSPY_RECONSTRUCT(Fixed<3>, Fixed<3>{}); break;
+    case 4: SSSPY_RECONSTRUCT(Fixed<4>, Fixed<4>{}); break;
+    case 5: SSSPY_RECONSTRUCT(Rolled5, Rolled5{}); break;
+    case 6: SSSPY_RECONSTRUCT(Rolled6, Rolled6{}); break;
+    case 7: SSSPY_RECONSTRUCT(Rolled7, Rolled7{}); break;
+    case 8: SSSPY_RECONSTRUCT(Rolled8, Rolled8{}); break;
+    default: SSSPY_RECONSTRUCT(Runtime, Runtime{L}); break;
+  }
+#undef SSSPY_RECONSTRUCT
+  return check_launch("k_psdtf_reconstruct");
 }
 
 int ssspy_matmul3(const void *A, const void *Bm, const void *C, void *out, long long n, int L,

@@ -731,6 +731,47 @@ __global__ __launch_bounds__(THREADS) void k_sum_logdet(const c128 *__restrict__
   if (threadIdx.x == 0) out[b] = total;
 }
 
+// out[i] = log|det A_i| of n matrices, the size (1..16) at run time, a lane per matrix in its private
+// memory: LU with partial pivoting (largest |re| + |im| of the column, the first one on ties).  A
+// column without a nonzero entry ends the elimination: -inf, as numpy.linalg.slogdet.
+__global__ __launch_bounds__(64) void k_logdet(const c128 *__restrict__ W, double *out, long long n,
+                                               int N) {
+  const long long i = (long long)blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  c128 A[SSSPY_RT_MAX_SOURCES * SSSPY_RT_MAX_SOURCES];
+  for (int e = 0; e < N * N; ++e) A[e] = W[i * (N * N) + e];
+  double s = 0.0;
+  for (int k = 0; k < N; ++k) {
+    int p = k;
+    double best = cabs1(A[k * N + k]);
+    for (int r = k + 1; r < N; ++r) {
+      const double v = cabs1(A[r * N + k]);
+      if (v > best) {
+        best = v;
+        p = r;
+      }
+    }
+    if (best == 0.0) {
+      s = -INFINITY;
+      break;
+    }
+    if (p != k)
+      for (int c = k; c < N; ++c) {
+        const c128 t = A[k * N + c];
+        A[k * N + c] = A[p * N + c];
+        A[p * N + c] = t;
+      }
+    const c128 piv = A[k * N + k];
+    s += log(hypot(piv.x, piv.y));
+    const c128 inv = crecip(piv);
+    for (int r = k + 1; r < N; ++r) {
+      const c128 f = cmul(A[r * N + k], inv);
+      for (int c = k + 1; c < N; ++c) cfms(A[r * N + c], f, A[k * N + c]);
+    }
+  }
+  out[i] = s;
+}
+
 }  // namespace ssspy
 
 using namespace ssspy;
@@ -1082,6 +1123,16 @@ int ssspy_sum_logdet(const void *W, double *out, int B, int F, int N, void *stre
   DISPATCH_N(N, hipLaunchKernelGGL((k_sum_logdet<NN>), grid, block, 0, as_stream(stream),
                                    (const c128 *)W, out, F));
   return check_launch("k_sum_logdet");
+}
+
+int ssspy_logdet(const void *W, double *out, long long n, int N, void *stream) {
+  SSSPY_REQUIRE(W && out && n > 0, "logdet: bad argument");
+  SSSPY_REQUIRE(n < 64LL * 2147483647LL, "logdet: n out of range");
+  if (N < 1 || N > SSSPY_RT_MAX_SOURCES)
+    return fail(SSSPY_ERR_UNSUPPORTED, "logdet takes matrices of 1 x 1 to 16 x 16");
+  hipLaunchKernelGGL(k_logdet, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, as_stream(stream),
+                     (const c128 *)W, out, n, N);
+  return check_launch("k_logdet");
 }
 
 }  // extern "C"

@@ -16,8 +16,10 @@ from .. import _device as dv
 from .. import _lib
 from .._device import ptr
 from . import prox  # noqa: F401
+from .polynomial import cbrt, solve_cubic
 
-__all__ = ["solve", "inv2", "eigh", "eigh2", "sqrtmh", "invsqrtmh", "gmeanmh", "lqpqm2", "prox"]
+__all__ = ["cbrt", "quadratic", "solve", "inv2", "eigh", "eigh2", "sqrtmh", "invsqrtmh", "gmeanmh",
+           "solve_cubic", "lqpqm2", "prox"]
 
 
 def _flat(a, tail):
@@ -257,3 +259,36 @@ def lqpqm2(H: np.ndarray, v: np.ndarray, z: np.ndarray, flooring_fn="default",
         warnings.warn("Newton-Raphson method did not converge in {} iterations.".format(max_iter),
                       UserWarning)
     return out
+
+
+def quadratic(X, A):
+    """Quadratic forms ``x^H A x`` of vectors ``X`` (*, n) against matrices ``A`` (*, n, n) -> (*,)
+    (ref: ssspy/linalg/quadratic.py:4-25; ``x^T A x`` for a real ``X``).
+
+    NumPy input is evaluated on the host and keeps its dtype.  complex128 torch tensors on the device
+    with the same leading shape and ``n`` in 1..16 are evaluated there, a lane per form, and a tensor
+    comes back; anything else on the device raises ``NotImplementedError``.
+    """
+    if type(X).__module__.split(".")[0] == "torch" or type(A).__module__.split(".")[0] == "torch":
+        return _quadratic_on_device(X, A)
+    Xh = X.conj() if np.iscomplexobj(X) else X
+    return (Xh[..., np.newaxis, :] @ A @ X[..., np.newaxis])[..., 0, 0]
+
+
+def _quadratic_on_device(X, A):
+    from .. import _ops
+
+    def limit(why):
+        return NotImplementedError(
+            "quadratic on the device takes complex128 tensors (*, n) and (*, n, n) on a HIP device "
+            "with n in 1..{}, got {} (convert to NumPy for the host form)".format(
+                _lib.RT_MAX_SOURCES, why))
+
+    for t in (X, A):
+        if type(t).__module__.split(".")[0] != "torch" or not t.is_cuda or t.dtype != dv.c128:
+            raise limit("{} {}".format(type(t).__name__, getattr(t, "dtype", "")))
+    if X.ndim < 1 or tuple(A.shape) != tuple(X.shape) + (X.shape[-1],):
+        raise limit("shapes {} and {}".format(tuple(X.shape), tuple(A.shape)))
+    if not 1 <= X.shape[-1] <= _lib.RT_MAX_SOURCES:
+        raise limit("n = {}".format(X.shape[-1]))
+    return _ops.quadratic_dev(X.contiguous(), A.contiguous())

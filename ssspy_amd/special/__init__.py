@@ -1,4 +1,5 @@
 from .flooring import add_flooring, identity, max_flooring
 from .psd import to_psd
+from .softmax import logsumexp, softmax
 
-__all__ = ["identity", "max_flooring", "add_flooring", "to_psd"]
+__all__ = ["identity", "max_flooring", "add_flooring", "to_psd", "logsumexp", "softmax"]
