@@ -51,6 +51,9 @@ ROUTE_NAMES = ["latency", "throughput", "grouped", "generic", "wide_basis", "run
 LAT, THR, GRP, GEN, WIDE, RTN = range(6)
 G2 = ((pr.GAUSS, 0.0), 2.0)  # (model, domain)
 K17_CHUNKED = (90, 4, 65, 16)  # (B, N, F, T): 450 bin tiles, 180 activation blocks per chunk
+MODELS = [((pr.GAUSS, 0.0), 2.0), ((pr.GAUSS | pr.ME, 0.0), 2.0), ((pr.GAUSS, 0.0), 1.0),
+          ((pr.GAUSS, 0.0), 1.3), ((pr.TMODEL, 3.0), 2.0), ((pr.GGD, 1.0), 2.0),
+          ((pr.GGD, 0.5), 2.0), ((pr.GGD, 1.2), 2.0)]
 
 
 # ------------------------------------------------------------------------------- device plumbing
@@ -122,17 +125,22 @@ def check(entry, route, got, ref, bar):
 @pytest.mark.parametrize("N", [2, 3, 4, 5, 8, 9, 16])
 def test_separate_and_compose(N):
     """separate (out of place and in place), compose_filters.  Per-N kernels to 8 sources, the
-    run-time-N kernels of wide_n.hip at 9 and 16.  T = 65: a second 64-frame block of one frame."""
+    run-time-N kernels of wide_n.hip at 9 and 16.  T = 65: a second 64-frame block of one frame.
+    At 9 and 16 sources also T = 257 and 300: k_separate_rt puts 256 threads along the frames, so
+    these take a second trip of its frame loop (of one frame, and of 44)."""
     _, dv, _, ops = _mods()
-    B, F, T = 2, 17, 65
-    X, W = pr.gen_spectrogram(10 + N, B, N, F, T), pr.gen_filters(10 + N, B, F, N)
-    Y, bar = pr.separate(X, W)
-    o = Out(X.shape, True)
-    ops.separate(up(X), up(W), out=o.t)
-    check("separate", "N={}".format(N), o.get(), Y, bar)
-    o = Out(X.shape, True, fill=X)
-    ops.separate(o.t, up(W), out=o.t)
-    check("separate_inplace", "N={}".format(N), o.get(), Y, bar)
+    B, F = 2, 17
+    W = pr.gen_filters(10 + N, B, F, N)
+    for T in (65,) + ((257, 300) if N > 8 else ()):
+        tag = "N={}".format(N) if T == 65 else "N={},T={}".format(N, T)
+        X = pr.gen_spectrogram(10 + N + (0 if T == 65 else T), B, N, F, T)
+        Y, bar = pr.separate(X, W)
+        o = Out(X.shape, True)
+        ops.separate(up(X), up(W), out=o.t)
+        check("separate", tag, o.get(), Y, bar)
+        o = Out(X.shape, True, fill=X)
+        ops.separate(o.t, up(W), out=o.t)
+        check("separate_inplace", tag, o.get(), Y, bar)
     G = pr.gen_filters(40 + N, B, F, N, 2)
     ref, bar = pr.compose_filters(G, W)
     o = Out(W.shape, True)
@@ -141,10 +149,12 @@ def test_separate_and_compose(N):
 
 
 @pytest.mark.parametrize("kind", [0, 1, 2])
-@pytest.mark.parametrize("N,T", [(2, 17), (3, 64), (4, 65), (5, 40), (8, 16), (9, 17), (16, 33)])
+@pytest.mark.parametrize("N,T", [(2, 17), (3, 64), (4, 65), (5, 40), (8, 16), (9, 17), (16, 33),
+                                 (9, 65), (16, 97)])
 def test_weighted_covariance(N, T, kind):
     """UNIT / FRAME / BIN_FRAME with S = 1 and S = N: per-N kernels (2..4), wide_cov.hip (5..8,
-    falling back to the per-N kernel where it declines the shape), wide_n.hip (9, 16)."""
+    falling back to the per-N kernel where it declines the shape), wide_n.hip (9, 16).  (9, 65) and
+    (16, 97) walk three and four 32-frame LDS tiles of k_cov_rt, the last of 1 frame."""
     _, dv, _, ops = _mods()
     B, F = 2, 17
     X = pr.gen_spectrogram(20 + N, B, N, F, T)
@@ -153,13 +163,120 @@ def test_weighted_covariance(N, T, kind):
         ref, bar = pr.weighted_covariance(X, w, kind, S)
         o = Out((B, F, S, N, N), True)
         ops.weighted_covariance(up(X), None if w is None else up(w), kind, S, out=o.t)
-        check("weighted_covariance_kind{}".format(kind), "N={} S={}".format(N, S), o.get(), ref, bar)
+        nt = "N={},T={}".format(N, T) if (N, T) in ((9, 65), (16, 97)) else "N={}".format(N)
+        check("weighted_covariance_kind{}".format(kind), "{} S={}".format(nt, S), o.get(), ref, bar)
+
+
+WIDE_COV_T = (1, 7, 8, 9, 15, 17, 63, 64, 65, 71, 129)
+KIND_NAMES = ["unit", "frame", "bin_frame"]
+
+
+def _wide_cov_weights(seed, kind, B, S, F, T):
+    return None if kind == 0 else pr.gen_weights(seed, (B, S, T) if kind == 1 else (B, S, F, T))
+
+
+@pytest.mark.parametrize("kind", [0, 1, 2])
+@pytest.mark.parametrize("N", [6, 7, 8])
+def test_wide_cov_frames_sets_and_channels(N, kind):
+    """k_wide_cov of wide_cov.hip alone (6..8 channels, at most 8 weight sets, a mixture below 4 GiB:
+    wide_weighted_cov_ok takes every shape here).  B F = 10 items are three workgroups, the last with
+    two live waves.  The frames walk in slabs of 8 through a ring of 8 slabs and 4 weight pairs:
+    T = 1..9 one or two slabs (every refill clamped), 15 and 17 a tail of 7 and of 1, 63..65 the
+    eighth slab short, full, and a second trip of the ring that holds one frame, 71 and 129 a ninth
+    and a seventeenth slab of 7 and of 1 (three trips; odd and even numbers of slab pairs; the weight
+    patch's two halves in turn).  S = 1, 3, N are the instances launch<1>, <3>, <6..8>; N = 6 and 7
+    leave tile rows to the descriptor's range check."""
+    _, dv, _, ops = _mods()
+    B, F = 2, 5
+    for T in WIDE_COV_T:
+        X = pr.gen_spectrogram(200 + 10 * N + T, B, N, F, T)
+        for S in ((1,) if kind == 0 else (1, 3, N)):
+            w = _wide_cov_weights(201 + N + T + S, kind, B, S, F, T)
+            ref, bar = pr.weighted_covariance(X, w, kind, S)
+            o = Out((B, F, S, N, N), True)
+            ops.weighted_covariance(up(X), None if w is None else up(w), kind, S, out=o.t)
+            check("wide_cov_" + KIND_NAMES[kind], "N={},S={} T={}".format(N, S, T), o.get(), ref, bar)
+
+
+def _narrow_spectrogram(seed, B, N, F, T):
+    """unit-variance columns with magnitudes over 1/2..2: every frame carries weight in every entry
+    of its covariance, so a frame that went missing is a gross error in all of them."""
+    rng = np.random.default_rng(seed)
+    X = (rng.standard_normal((B, N, F, T)) + 1j * rng.standard_normal((B, N, F, T))) \
+        * np.exp2(rng.uniform(-1, 1, (B, N, F, T)))
+    return X.astype(np.complex128)
+
+
+@pytest.mark.parametrize("kind", [1, 2])
+@pytest.mark.parametrize("T", [9, 65])
+def test_wide_cov_nonfinite_neighbour(T, kind):
+    """The tail slab of a row of 9 or 65 frames is loaded whole: 7 frames of it are the first frames
+    of the row behind -- the same channel's next bin for the samples; the next set (FRAME) or the next
+    bin of the set (BIN_FRAME) for the weights.  One sample and one weight there are Inf.  The bins and
+    sets in front of them must come out finite and within the bar (a masked weight alone would leave
+    0 * Inf), the poisoned bin and set themselves non-finite (so the Inf did reach the device)."""
+    _, dv, _, ops = _mods()
+    B, N, F = 2, 8, 5
+    X = pr.gen_spectrogram(260 + T, B, N, F, T)
+    for S in (3, N):
+        w = _wide_cov_weights(261 + T + S, kind, B, S, F, T)
+        ref, bar = pr.weighted_covariance(X, w, kind, S)  # (of the clean inputs: what is checked
+        Xp, wp = X.copy(), w.copy()                        #  does not depend on the poisoned ones)
+        Xp[0, 3, 2, 2] = np.inf   # read by the tail of (mixture 0, channel 3, bin 1)
+        dirty = np.zeros((B, F, S), bool)
+        dirty[0, 2, :] = True
+        if kind == 1:
+            wp[0, 1, 1] = np.inf  # read by the tail of set 0, every bin
+            dirty[0, :, 1] = True
+        else:
+            wp[0, 1, 4, 1] = np.inf  # read by the tail of (set 1, bin 3)
+            wp[0, 1, 0, 1] = np.inf  # read by the tail of (set 0, bin 4), across the sets
+            dirty[0, 4, 1] = dirty[0, 0, 1] = True
+        o = Out((B, F, S, N, N), True)
+        ops.weighted_covariance(up(Xp), up(wp), kind, S, out=o.t)
+        got = o.get()
+        assert not np.any(np.isfinite(got[dirty][:, 3, 3])), "the Inf did not reach its own bin / set"
+        check("wide_cov_" + KIND_NAMES[kind] + "_inf_neighbour", "N={},S={},T={}".format(N, S, T),
+              got[~dirty], ref[~dirty], bar[~dirty])
+
+
+@pytest.mark.parametrize("kind", [1, 2])
+@pytest.mark.parametrize("T", [9, 65])
+def test_wide_cov_last_weight(T, kind):
+    """T odd: the last frame's weight of a mixture's last set is the first half of a 16-byte load
+    whose second half lies past the mixture's weights (past the descriptor; mixture 1's weights also
+    start 8 bytes off a 16-byte boundary, S T and S F T being odd).  That weight is 2^20 times the
+    others, on samples of even magnitude: were the load dropped as a whole, every entry of the last
+    set would be off by about its own size."""
+    _, dv, _, ops = _mods()
+    B, N, F, S = 2, 8, 5, 3
+    X = _narrow_spectrogram(270 + T, B, N, F, T)
+    rng = np.random.default_rng(271 + T + kind)
+    w = np.exp2(rng.uniform(-1, 1, (B, S, T) if kind == 1 else (B, S, F, T)))
+    w.reshape(B, -1)[:, -1] *= 2.0 ** 20
+    ref, bar = pr.weighted_covariance(X, w, kind, S)
+    # what that one frame contributes to the entries it reaches: at least 1e6 bars, in every one
+    short = pr.weighted_covariance(X[..., :-1], w[..., :-1], kind, S)[0] * LD(T - 1) / LD(T)
+    sel = (slice(None), -1 if kind == 2 else slice(None), -1)
+    assert np.all(np.abs(ref - short)[sel] > 1e6 * bar[sel])
+    o = Out((B, F, S, N, N), True)
+    ops.weighted_covariance(up(X), up(w), kind, S, out=o.t)
+    check("wide_cov_" + KIND_NAMES[kind] + "_last_weight", "N={},S={},T={}".format(N, S, T), o.get(),
+          ref, bar)
 
 
 @pytest.mark.parametrize("N", [2, 3, 4, 6, 9, 16])
 def test_cross_covariance_and_congruence(N):
+    """At 9 and 16 sources also T = 65 and 97: three and four 32-frame LDS tiles of k_cov_rt with
+    both operands staged, the last tile of one frame."""
     _, dv, _, ops = _mods()
     B, F, T = 2, 17, 33
+    for T2 in {9: (65,), 16: (97,)}.get(N, ()):
+        X, Z = pr.gen_spectrogram(30 + N + T2, B, N, F, T2), pr.gen_spectrogram(31 + N + T2, B, N, F, T2)
+        ref, bar = pr.cross_covariance(X, Z)
+        o = Out((B, F, N, N), True)
+        ops.cross_covariance(up(X), up(Z), out=o.t)
+        check("cross_covariance", "N={},T={}".format(N, T2), o.get(), ref, bar)
     X, Z = pr.gen_spectrogram(30 + N, B, N, F, T), pr.gen_spectrogram(31 + N, B, N, F, T)
     ref, bar = pr.cross_covariance(X, Z)
     o = Out((B, F, N, N), True)
@@ -200,12 +317,16 @@ def test_fold_scalar_slots(total, nslots):
 
 # ------------------------------------------------------------------------------- ILRMA passes
 def _ilrma_passes(B, N, F, T, K, route, model=G2[0], domain=2.0, flooring=MAXF, chunks=None,
-                  floor_inputs=False, seed=0, split=None):
-    """basis, activation, loss, covariance and ISS weights of one shape, with and without a filter."""
+                  floor_inputs=False, seed=0, split=None, own_line=False):
+    """basis, activation, loss, covariance and ISS weights of one shape, with and without a filter.
+    own_line: the case keeps a line of its own per entry point in the profile (shape, model and floor
+    join the route in the key) instead of counting towards its route's worst case."""
     _, dv, _, ops = _mods()
     got_route, got_chunks, plan = ops.ilrma_route(B, N, F, T, K, domain, model)
     assert got_route == route, "shape reaches {} instead of {}".format(
         ROUTE_NAMES[got_route], ROUTE_NAMES[route])
+    print("route asserted: {} for B{} N{} F{} T{} K{} model {} domain {}".format(
+        ROUTE_NAMES[route], B, N, F, T, K, model, domain))
     if chunks == "one":
         assert got_chunks == 1
     elif chunks == "many":
@@ -229,6 +350,10 @@ def _ilrma_passes(B, N, F, T, K, route, model=G2[0], domain=2.0, flooring=MAXF, 
     ws, wsb = ops.ilrma_workspace(B, N, F, T, K, dv.device())
     kind = model[0] & 0xff
     mname = "m{}p{}d{}f{}".format(model[0], model[1], domain, flooring[0])
+    label = tag + " " + mname
+    if own_line:
+        label = "{}[B{},N{},F{},T{},K{},{}{}]".format(ROUTE_NAMES[route], B, N, F, T, K, mname,
+                                                     ",floor_inputs" if floor_inputs else "")
     Xd, Wd, bd, ad = up(X), up(W), up(basis), up(act)
     for Wh, Wdev, wt in ((W, Wd, "W"), (None, None, "noW")):
         ref, bar = pr.ilrma_update_basis(X, Wh, basis, act, domain, model, flooring, fast_pow=fast)
@@ -237,17 +362,17 @@ def _ilrma_passes(B, N, F, T, K, route, model=G2[0], domain=2.0, flooring=MAXF, 
             assert 0.05 < fl < 0.95, "floored share {}".format(fl)
         o = Out(basis.shape, fill=basis)
         ops.ilrma_update_basis(Xd, Wdev, o.t, ad, domain, flooring, ws, wsb, model=model)
-        check("ilrma_update_basis_" + wt, tag + " " + mname, o.get(), ref, bar)
+        check("ilrma_update_basis_" + wt, label, o.get(), ref, bar)
         ref, bar = pr.ilrma_update_activation(X, Wh, basis, act, domain, model, flooring,
                                               fast_pow=fast)
         o = Out(act.shape, fill=act)
         ops.ilrma_update_activation(Xd, Wdev, bd, o.t, domain, flooring, ws, wsb, model=model)
-        check("ilrma_update_activation_" + wt, tag + " " + mname, o.get(), ref, bar)
+        check("ilrma_update_activation_" + wt, label, o.get(), ref, bar)
         if not floor_inputs:
             ref, bar = pr.ilrma_loss_data(X, Wh, basis, act, domain, model, fast_pow=fast)
             o = Out((B,))
             ops.ilrma_loss_data(Xd, Wdev, bd, ad, domain, out=o.t, model=model)
-            check("ilrma_loss_data_" + wt, tag + " " + mname, o.get(), ref, bar)
+            check("ilrma_loss_data_" + wt, label, o.get(), ref, bar)
     # covariance: the filter is read by the heavy-tailed models only
     Wh, Wdev = (None, None) if kind == pr.GAUSS else (W, Wd)
     ref, bar = pr.ilrma_weighted_covariance(X, Wh, basis, act, domain, model, flooring,
@@ -255,16 +380,16 @@ def _ilrma_passes(B, N, F, T, K, route, model=G2[0], domain=2.0, flooring=MAXF, 
     o = Out((B, F, N, N, N), True)
     ops.ilrma_weighted_covariance(Xd, bd, ad, domain, ws, wsb, out=o.t, W=Wdev, model=model,
                                   flooring=flooring)
-    check("ilrma_weighted_covariance", tag + " " + mname, o.get(), ref, bar)
+    check("ilrma_weighted_covariance", label, o.get(), ref, bar)
     ref, bar = pr.ilrma_iss_weight(X, basis, act, domain, model, flooring)
     o = Out((B, N, F, T))
     ops.ilrma_iss_weight(bd, ad, domain, out=o.t, Y=Xd, model=model, flooring=flooring)
-    check("ilrma_iss_weight", tag + " " + mname, o.get(), ref, bar)
+    check("ilrma_iss_weight", label, o.get(), ref, bar)
     Ypow = np.abs(X) ** 2
     ref, bar = pr.ilrma_iss_weight(None, basis, act, domain, model, flooring, Ypow=Ypow)
     o = Out((B, N, F, T))
     ops.ilrma_iss_weight(bd, ad, domain, out=o.t, model=model, flooring=flooring, Ypow=up(Ypow))
-    check("ilrma_iss_weight_power", tag + " " + mname, o.get(), ref, bar)
+    check("ilrma_iss_weight_power", label, o.get(), ref, bar)
 
 
 @pytest.mark.parametrize("N", [2, 3, 4])
@@ -322,20 +447,62 @@ def test_ilrma_wide_basis(K):
     _ilrma_passes(2, 3, 17, 17, K, WIDE)
 
 
+@pytest.mark.parametrize("K", [33, 64, 65])
+def test_ilrma_wide_basis_edge_tiles(K):
+    """k_gemm_f64 past one workgroup tile.  F = 100, T = 97: two 64 x 64 tiles each way, the edge
+    tiles with 36 and 33 live rows / columns -- all four waves and both 16-row sub-tiles of each hold
+    data next to masked lanes, blockIdx.x and .y reach 1.  The depth Kd is K for R = T V (33: two
+    full stages and one of 1; 64: four full stages, no remainder; 65: four and one of 1), T = 97 for
+    the basis products (seven stages, the A side kd-contiguous, the B side outer-contiguous) and
+    F = 100 for the activation products (seven stages, both sides outer-contiguous; K is the row
+    count there: one tile of 33 rows, one full tile, a second tile of one row).  B N = 3 sources:
+    the numerator / denominator pairs of the dual launches sit at odd and even g >> 1."""
+    _ilrma_passes(1, 3, 100, 97, K, WIDE, own_line=True)
+
+
+@pytest.mark.parametrize("F,T", [(64, 65), (65, 64)])
+def test_ilrma_wide_basis_tile_boundaries(F, T):
+    """Exactly one full tile one way, one tile and a single row / column the other."""
+    _ilrma_passes(1, 2, F, T, 33, WIDE, own_line=True)
+
+
+@pytest.mark.parametrize("model,domain", MODELS)
+def test_ilrma_wide_basis_models(model, domain):
+    """Every model through the epilogues of k_gemm_f64 (EPI_AB, EPI_PHI, EPI_LOSS) and k_mu_update;
+    F = 40, T = 36: waves 0..3 hold 32 x 32, 32 x 4, 8 x 32 and 8 x 4 live entries."""
+    _ilrma_passes(1, 3, 40, 36, 33, WIDE, model=model, domain=domain, own_line=True)
+
+
+@pytest.mark.parametrize("flooring", [NOF, MAXF, ADDF])
+@pytest.mark.parametrize("model,domain", [MODELS[0], MODELS[7]])
+def test_ilrma_wide_basis_floors(model, domain, flooring):
+    """k_mu_update's floor with updated values on both sides of eps (test_pass_reference_cpu.py checks
+    the floored share of these inputs with the reference alone)."""
+    _ilrma_passes(1, 3, 40, 36, 33, WIDE, model=model, domain=domain, flooring=flooring,
+                  floor_inputs=True, own_line=True)
+
+
 @pytest.mark.parametrize("N", [9, 16])
 def test_ilrma_runtime_source_count(N):
     _ilrma_passes(1, N, 17, 17, 7, RTN)
+
+
+@pytest.mark.parametrize("B,N,F,T,K", [(1, 9, 70, 67, 7), (1, 9, 70, 67, 40), (1, 16, 3, 300, 7),
+                                       (2, 9, 3, 257, 7)])
+def test_ilrma_runtime_source_count_tiles_and_frames(B, N, F, T, K):
+    """F = 70, T = 67: edge tiles of 6 and 3 rows / columns.  At K = 7 the NMF passes of 9 = 3 x 3 and
+    16 = 4 x 4 sources are walked in groups by the tuned kernels (source_group) and k_gemm_f64 runs for
+    the loss alone (EPI_LOSS, Kd = 7: a single short stage); K = 40 (both reasons for the route at
+    once) puts every pass on the dense products, three stages deep.  T = 300 and 257 at F = 3: the
+    frame loops of wide_n.hip (256 threads along frames: separate, its power form in front of the
+    filtered passes) take a second trip, k_cov_rt ten and nine frame tiles."""
+    _ilrma_passes(B, N, F, T, K, RTN, own_line=True)
 
 
 @pytest.mark.parametrize("N", [2, 3, 4, 5, 6, 7, 8])
 def test_ilrma_generic_kernels(N):
     """The t model at domain 1 is off the tuned path: the per-N kernels of ilrma_kernels.hip."""
     _ilrma_passes(2, N, 17, 17, 7, GEN, model=(pr.TMODEL, 3.0), domain=1.0)
-
-
-MODELS = [((pr.GAUSS, 0.0), 2.0), ((pr.GAUSS | pr.ME, 0.0), 2.0), ((pr.GAUSS, 0.0), 1.0),
-          ((pr.GAUSS, 0.0), 1.3), ((pr.TMODEL, 3.0), 2.0), ((pr.GGD, 1.0), 2.0),
-          ((pr.GGD, 0.5), 2.0), ((pr.GGD, 1.2), 2.0)]
 
 
 @pytest.mark.parametrize("B,route", [(2, LAT), (180, THR)])
@@ -531,14 +698,18 @@ def test_ilrma_ip1_update_fused(B, N, K, route, model, domain, normalize):
 
 # ------------------------------------------------------------------------------- AuxIVA passes
 @pytest.mark.parametrize("B,N,F,T", [(1, 2, 17, 65), (2, 3, 1, 1), (2, 4, 33, 17), (128, 2, 17, 16),
-                                     (3, 6, 16, 64), (2, 8, 15, 2), (1, 9, 17, 15), (1, 16, 17, 33)])
+                                     (3, 6, 16, 64), (2, 8, 15, 2), (1, 9, 17, 15), (1, 16, 17, 33),
+                                     (1, 9, 17, 257), (1, 9, 17, 300), (1, 16, 17, 257),
+                                     (1, 16, 17, 300)])
 def test_iva_frame_power(B, N, F, T):
     """iva_frame_power with and without a filter, separate_frame_power (to 8 sources).  B = 128 takes
     the thread-per-frame kernel, the others the four-wave form with folded bin chunks; 9 and 16
-    sources the run-time-N kernel."""
+    sources the run-time-N kernel, a thread per frame in blocks of 256: T = 257 and 300 are a second
+    frame block of 1 and of 44 threads."""
     _, dv, _, ops = _mods()
     X, W = pr.gen_spectrogram(90 + N, B, N, F, T), pr.gen_filters(90 + N, B, F, N)
-    tag = "B{} N{} F{} T{}".format(B, N, F, T)
+    # (the cases of a second frame block keep profile lines of their own)
+    tag = ("B{},N{},F{},T{}" if T > 256 else "B{} N{} F{} T{}").format(B, N, F, T)
     for Wh, wt in ((None, "noW"), (W, "W")):
         ref, bar = pr.iva_frame_power(X, Wh)
         o = Out((B, N, T))

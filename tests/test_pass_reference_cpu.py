@@ -102,7 +102,8 @@ def test_shared_reference_matches_oracle(N):
 
 # ------------------------------------------------------------------------------- attainable bars
 SHAPES = [(3, 3, 17, 40, 12), (2, 2, 1, 1, 1), (2, 2, 15, 2, 7), (2, 2, 16, 65, 7), (2, 4, 17, 64, 16),
-          (2, 4, 65, 40, 12), (2, 3, 17, 17, 33), (1, 8, 17, 17, 7), (1, 16, 17, 17, 7)]
+          (2, 4, 65, 40, 12), (2, 3, 17, 17, 33), (1, 8, 17, 17, 7), (1, 16, 17, 17, 7),
+          (1, 3, 40, 36, 33)]
 
 
 # the large-batch legs of the GPU file run the Gauss model at domain 2 only; so do they here
@@ -152,6 +153,65 @@ def test_float64_stays_inside_the_bars_at_the_floor(model, domain, flooring):
             inside(fn(X, Wb, basis, act, domain, model, flooring, dtype=np.float64)[0], ref, bar)
             if flooring[0] == pr.FLOOR_MAX:
                 assert 0.05 < float(np.mean(ref == LD(pr.EPS))) < 0.95
+
+
+# the edge-tile, tile-boundary and long-frame shapes of the dense-product routes (n_basis >= 33, or 9..16
+# sources): the GPU file runs the Gauss model at domain 2 there; so do they here
+DENSE_SHAPES = [(1, 3, 100, 97, 33), (1, 3, 100, 97, 64), (1, 3, 100, 97, 65), (1, 2, 64, 65, 33),
+                (1, 2, 65, 64, 33), (1, 9, 70, 67, 7), (1, 9, 70, 67, 40), (1, 16, 3, 300, 7),
+                (2, 9, 3, 257, 7)]
+
+
+@pytest.mark.parametrize("B,N,F,T,K", DENSE_SHAPES)
+def test_float64_stays_inside_the_ilrma_bars_at_the_dense_shapes(B, N, F, T, K):
+    X, W, basis, act = _inputs(B * 7 + N * 5 + F * 3 + T * 2 + K, B, N, F, T, K)
+    model, domain = MODELS[0]
+    for Wb in (W, None):
+        for fn in (pr.ilrma_update_basis, pr.ilrma_update_activation, pr.ilrma_weighted_covariance):
+            ref, bar = fn(X, Wb, basis, act, domain, model, MAXF)
+            inside(fn(X, Wb, basis, act, domain, model, MAXF, dtype=np.float64)[0], ref, bar)
+        ref, bar = pr.ilrma_loss_data(X, Wb, basis, act, domain, model)
+        inside(pr.ilrma_loss_data(X, Wb, basis, act, domain, model, dtype=np.float64)[0], ref, bar)
+    ref, bar = pr.ilrma_iss_weight(X, basis, act, domain, model, MAXF)
+    inside(pr.ilrma_iss_weight(X, basis, act, domain, model, MAXF, dtype=np.float64)[0], ref, bar)
+
+
+@pytest.mark.parametrize("flooring", [NOF, MAXF, ADDF])
+@pytest.mark.parametrize("model,domain", [MODELS[0], MODELS[7]])
+def test_floor_inputs_straddle_eps_at_33_bases(model, domain, flooring):
+    """The floor case of the dense-product route, (B, N, F, T, K) = (1, 3, 40, 36, 33) from the seed the
+    GPU file derives for it: with the reference alone, between 5 % and 95 % of the updated basis ends
+    at the MAX floor (the condition the GPU case asserts), with and without a filter, and float64
+    stays inside the bars on both sides of eps."""
+    B, N, F, T, K = 1, 3, 40, 36, 33
+    seed = B * 7 + N * 5 + F * 3 + T * 2 + K
+    X = pr.gen_spectrogram(seed, B, N, F, T) * np.exp2(-44)
+    W = pr.gen_filters(seed, B, F, N)
+    basis, act = pr.gen_floor_nmf(seed, B, N, F, T, K)
+    for Wb in (W, None):
+        for fn in (pr.ilrma_update_basis, pr.ilrma_update_activation):
+            for fast in (False, True):
+                ref, bar = fn(X, Wb, basis, act, domain, model, flooring, fast_pow=fast)
+                inside(fn(X, Wb, basis, act, domain, model, flooring, dtype=np.float64,
+                          fast_pow=fast)[0], ref, bar)
+            if flooring[0] == pr.FLOOR_MAX:
+                assert 0.05 < float(np.mean(ref == LD(pr.EPS))) < 0.95
+
+
+@pytest.mark.parametrize("N", [6, 7, 8])
+def test_float64_stays_inside_the_covariance_bars_at_any_set_count(N):
+    """weighted_covariance with 1 < S < N weight sets and the frame counts of the matrix-core
+    covariance cases (T = 1 .. 129), every kind: the (T + 6) u bar holds for float64 NumPy."""
+    B, F = 2, 5
+    for T in (1, 7, 8, 9, 15, 17, 63, 64, 65, 71, 129):
+        X = pr.gen_spectrogram(200 + 10 * N + T, B, N, F, T)
+        for kind in (0, 1, 2):
+            for S in ((1,) if kind == 0 else (1, 3, N)):
+                w = None if kind == 0 else pr.gen_weights(
+                    201 + N + T + S, (B, S, T) if kind == 1 else (B, S, F, T))
+                ref, bar = pr.weighted_covariance(X, w, kind, S)
+                assert ref.shape == (B, F, S, N, N)
+                inside(pr.weighted_covariance(X, w, kind, S, dtype=np.float64)[0], ref, bar)
 
 
 @pytest.mark.parametrize("N", [2, 4, 6, 9, 16])
