@@ -1516,6 +1516,35 @@ int ssspy_logsumexp(const double *X, double *out, long long outer, int len, long
  * replaces: ssspy/linalg/quadratic.py:4-25. */
 int ssspy_quadratic(const void *X, const void *A, void *out, long long n, int N, void *stream);
 
+/* ------------------------------------------------------------------ OverIVA (csrc/overiva.hip)
+ * Overdetermined AuxIVA-IP1 (Scheibler & Ono, WASPAA 2019): N <= M demixing rows W_t; the full filter
+ * W (B, F, M, M) = [W_t ; [J, -I]] carries a Gaussian background J (M - N, N) fixed by
+ * [J, -I] C W_t^H = 0, J = (E2 C W_t^H)(E1 C W_t^H)^-1.  2 <= M <= 16, 1 <= N <= M, else
+ * SSSPY_ERR_UNSUPPORTED.  (Added at SSSPY_ABI_VERSION 11 without a bump: no existing argument list
+ * changed.) */
+
+/* r2 (B, N, T) = sum_i |y_nij|^2 with y = W_t x; Y (B, N, F, T) receives y when not NULL.  The N x M
+ * rows of bin (b, i) start at Wt + (b F + i) w_stride complex numbers (N M for a packed filter, M M for
+ * the first rows of the full one).  Bin chunks are folded in chunk order: no fp64 atomics, the same
+ * bits on every run.  `workspace`: ssspy_overiva_frame_power_workspace_bytes(...) bytes (may be 0). */
+size_t ssspy_overiva_frame_power_workspace_bytes(int B, int N, int F, int T);
+int ssspy_overiva_frame_power(const void *X, const void *Wt, long long w_stride, void *Y, double *r2,
+                              int B, int M, int N, int F, int T, void *workspace,
+                              size_t workspace_bytes, void *stream);
+
+/* One sweep on W (B, F, M, M) in place.  With logdet / trace (B each; both or neither) the sums over
+ * the bins of log|det W| and Re tr(U C U^H), U = [J, -I], of the filter AS IT COMES IN are left there
+ * first (`workspace`: ssspy_overiva_step_workspace_bytes(B, F) bytes).  Then, with V (B, F, N, M, M)
+ * the weighted covariances of the N sources: for n = 0..N-1 in order row n <- IP1 (the arithmetic of
+ * ssspy_update_by_ip1 on the full filter with V_n) and rows N.. <- [J, -I] re-formed from C
+ * (B, F, M, M).  With V == NULL no row is updated; rows N.. are re-formed only when logdet is NULL too
+ * (the state a call starts from).  A pivot of either solve that is not above 16 eps size times the
+ * largest entry of its column before the elimination bumps info[0]. */
+size_t ssspy_overiva_step_workspace_bytes(int B, int F);
+int ssspy_overiva_step(void *W, const void *V, const void *C, int B, int F, int M, int N,
+                       int floor_kind, double floor_eps, int *info, double *logdet, double *trace,
+                       void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ STFT / ISTFT
  * The transforms the reference's workflow takes from SciPy either side of a separator
  * (tests/package/bss/test_ilrma.py, test_iva.py, test_mnmf.py: scipy.signal.stft(x, window="hann",

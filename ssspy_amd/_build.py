@@ -47,6 +47,7 @@ def _units():
         ("iva_kernels.hip", "iva_kernels.o", []),
         ("grad_iva.hip", "grad_iva.o", []),
         ("fast_iva.hip", "fast_iva.o", []),
+        ("overiva.hip", "overiva.o", []),
         ("fdica.hip", "fdica.o", []),
         ("ica.hip", "ica.o", []),
         ("pdsbss.hip", "pdsbss.o", []),

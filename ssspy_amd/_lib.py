@@ -150,6 +150,10 @@ PROTOTYPES = {
     "ssspy_separate_frame_power": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _z, _p]),
     "ssspy_iva_weight": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _d, _p]),
     "ssspy_iva_loss_data": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "ssspy_overiva_frame_power_workspace_bytes": (_z, [_i, _i, _i, _i]),
+    "ssspy_overiva_frame_power": (_i, [_p, _p, _q, _p, _p, _i, _i, _i, _i, _i, _p, _z, _p]),
+    "ssspy_overiva_step_workspace_bytes": (_z, [_i, _i]),
+    "ssspy_overiva_step": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _d, _p, _p, _p, _p, _z, _p]),
     "ssspy_iva_score_weight": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _d, _p]),
     "ssspy_iva_grad_step_logdet_slots": (_i, [_i, _i, _i]),
     "ssspy_iva_grad_step": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _d, _p, _p, _q, _p]),

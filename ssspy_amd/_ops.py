@@ -696,6 +696,35 @@ def iva_loss_data(r2, variance, n_bins, contrast, out=None):
     return out
 
 
+def overiva_frame_power(X, W, n_sources, r2=None, Y=None, packed=False):
+    """r2 (B, N, T) = sum_i |W_t x|^2 with W_t the first N rows of the full filter W (B, F, M, M),
+    or W itself (B, F, N, M) when ``packed``; ``Y`` (B, N, F, T), when given, receives W_t x in the
+    same walk."""
+    B, M, F, T = X.shape
+    N = int(n_sources)
+    if r2 is None:
+        r2 = dv.empty((B, N, T), dv.f64, X.device)
+    ws, ws_bytes = _scratch(_L().ssspy_overiva_frame_power_workspace_bytes(B, N, F, T), X.device)
+    _lib.check(_L().ssspy_overiva_frame_power(ptr(X), ptr(W), (N if packed else M) * M, ptr(Y),
+                                              ptr(r2), B, M, N, F, T, ptr(ws), ws_bytes, _st()),
+               "overiva_frame_power")
+    return r2
+
+
+def overiva_step(W_full, V, C, n_sources, flooring, info=None, logdet=None, trace=None):
+    """One OverIVA sweep on the full filter (B, F, M, M) in place (see the header): the loss terms of
+    the filter as it comes in into ``logdet`` / ``trace`` (B,) when given, the N row updates from
+    ``V`` (B, F, N, M, M) when given, the background rows re-formed from ``C`` (B, F, M, M)."""
+    B, F, M, _ = W_full.shape
+    ws, ws_bytes = (None, 0)
+    if logdet is not None:
+        ws, ws_bytes = _scratch(_L().ssspy_overiva_step_workspace_bytes(B, F), W_full.device)
+    _lib.check(_L().ssspy_overiva_step(ptr(W_full), ptr(V), ptr(C), B, F, M, int(n_sources),
+                                       flooring[0], flooring[1], ptr(info), ptr(logdet), ptr(trace),
+                                       ptr(ws), ws_bytes, _st()), "overiva_step")
+    return W_full
+
+
 def iva_score_weight(r2, n_bins, contrast, flooring, weight=None, variance=None):
     """Score weights of the gradient IVA classes: Laplace 1 / floor(r), Gauss 1 / alpha with the
     variance alpha = r2 / n_bins refreshed in ``variance``; (B, N, T)."""

@@ -1,4 +1,4 @@
-from . import admmbss, base, cacgmm, fdica, hva, ica, ilrma, ipsdta, iva, mnmf, pdsbss, proxbss
+from . import admmbss, base, cacgmm, fdica, hva, ica, ilrma, ipsdta, iva, mnmf, overiva, pdsbss, proxbss
 from .admmbss import ADMMBSS, ADMMBSSBase, MaskingADMMBSS
 from .base import IterativeMethodBase
 from .cacgmm import CACGMM, CACGMMBase
@@ -15,6 +15,7 @@ from .fdica import (
 from .hva import HVA, MaskingADMMHVA, MaskingPDSHVA
 from .ica import FastICA, GradICA, GradLaplaceICA, NaturalGradICA, NaturalGradLaplaceICA
 from .ipsdta import TIPSDTA, BlockDecompositionIPSDTABase, GaussIPSDTA, IPSDTABase
+from .overiva import OverGaussIVA, OverIVABase, OverLaplaceIVA
 from .pdsbss import PDSBSS, MaskingPDSBSS, PDSBSSBase
 from .proxbss import ProxBSSBase
 
@@ -23,5 +24,5 @@ __all__ = ["IterativeMethodBase", "CACGMM", "CACGMMBase", "IPSDTABase", "BlockDe
            "AuxFDICA", "GradLaplaceFDICA", "NaturalGradLaplaceFDICA", "AuxLaplaceFDICA",
            "ProxBSSBase", "PDSBSSBase", "PDSBSS", "MaskingPDSBSS", "MaskingPDSHVA", "HVA", "ADMMBSSBase", "ADMMBSS",
            "MaskingADMMBSS", "MaskingADMMHVA", "GradICA", "NaturalGradICA", "FastICA", "GradLaplaceICA",
-           "NaturalGradLaplaceICA", "admmbss", "base", "cacgmm",
-           "fdica", "hva", "ica", "ilrma", "ipsdta", "iva", "mnmf", "pdsbss", "proxbss"]
+           "NaturalGradLaplaceICA", "OverIVABase", "OverLaplaceIVA", "OverGaussIVA", "admmbss", "base", "cacgmm",
+           "fdica", "hva", "ica", "ilrma", "ipsdta", "iva", "mnmf", "overiva", "pdsbss", "proxbss"]
