@@ -22,6 +22,7 @@ import warnings
 from typing import Optional, Union
 
 import numpy as np
+import torch
 
 from . import _device as dv
 from . import _lib
@@ -151,10 +152,41 @@ def _stream():
     return dv.stream_handle()
 
 
+# a launch grid is (n_frames, C, 1): HIP takes at most 65535 workgroups along y
+_MAX_GRID_Y = 65535
+
+
+def _on_device(a, dtype, torch_dtype, what, core, real_only):
+    """The kernels read `dtype` through a raw pointer: anything else is converted first (a tensor on
+    the device, where the cast is plumbing), and a tensor the device cannot read is refused as
+    ``_bind_input`` refuses it.  The checks come before the upload or the cast: what is refused has
+    touched no device.  `core`: the trailing axes of one signal; the others index the launch grid."""
+    is_tensor = isinstance(a, torch.Tensor)
+    if is_tensor:
+        if not a.is_cuda:
+            raise ValueError("a tensor input must be on the HIP device")
+        is_complex = a.is_complex()
+    else:
+        a = np.asarray(a)
+        is_complex = np.iscomplexobj(a)
+    if real_only and is_complex:
+        raise ValueError("{} takes a real signal, got {}".format(what, a.dtype))
+    if a.ndim < core:
+        raise ValueError("{} takes at least {} axes, got shape {}".format(what, core, tuple(a.shape)))
+    C = int(np.prod(a.shape[: a.ndim - core], dtype=np.int64))
+    if C > _MAX_GRID_Y:
+        raise ValueError("{}: the leading axes hold {} signals, a launch takes at most {}".format(
+            what, C, _MAX_GRID_Y))
+    if is_tensor:
+        return a if a.dtype == torch_dtype else a.to(torch_dtype)
+    return dv.to_device(a, dtype=dtype)
+
+
 def stft(x, n_fft: int, hop_length: Optional[int] = None, window="hann", device_output=False):
-    """x (..., n_samples) real -> (..., n_fft // 2 + 1, n_frames) complex128."""
+    """x (..., n_samples) real -> (..., n_fft // 2 + 1, n_frames) complex128.  ``x``: an array (or
+    what ``np.asarray`` takes) or a tensor on the HIP device, of any real dtype."""
     hop = n_fft // 2 if hop_length is None else int(hop_length)
-    xd = dv.to_device(x, dtype=np.float64) if isinstance(x, np.ndarray) else x
+    xd = _on_device(x, np.float64, dv.f64, "stft", 1, real_only=True)
     lead, L = tuple(xd.shape[:-1]), int(xd.shape[-1])
     if n_fft > L:
         # a signal shorter than one window: scipy.signal.stft shrinks nperseg to the signal (with this
@@ -184,10 +216,11 @@ def stft(x, n_fft: int, hop_length: Optional[int] = None, window="hann", device_
 
 def istft(Z, n_fft: int, hop_length: Optional[int] = None, window="hann", device_output=False):
     """Z (..., n_fft // 2 + 1, n_frames) complex -> (..., n_samples) real (trim to the original
-    length yourself, as with SciPy: the forward transform pads to a whole number of hops)."""
+    length yourself, as with SciPy: the forward transform pads to a whole number of hops).  ``Z``: an
+    array or a tensor on the HIP device, of any real or complex dtype."""
     hop = n_fft // 2 if hop_length is None else int(hop_length)
     w = _window(window, n_fft)
-    Zd = dv.to_device(Z, dtype=np.complex128) if isinstance(Z, np.ndarray) else Z
+    Zd = _on_device(Z, np.complex128, dv.c128, "istft", 2, real_only=False)
     lead, F, n_frames = tuple(Zd.shape[:-2]), int(Zd.shape[-2]), int(Zd.shape[-1])
     if F != n_fft // 2 + 1:
         raise ValueError("expected {} bins for n_fft = {}, got {}".format(n_fft // 2 + 1, n_fft, F))
