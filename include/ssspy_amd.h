@@ -1545,6 +1545,53 @@ int ssspy_overiva_step(void *W, const void *V, const void *C, int B, int F, int 
                        int floor_kind, double floor_eps, int *info, double *logdet, double *trace,
                        void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ WPE (csrc/wpe.hip)
+ * Dereverberation by weighted prediction error: Nakatani, Yoshioka, Kinoshita, Miyoshi, Juang,
+ * "Speech dereverberation based on variance-normalized delayed linear prediction", IEEE TASLP 18(7),
+ * 2010.  Per bin, with x_t the M channels of frame t, xs_t in C^L (L = taps M) the stacked history,
+ * entry k M + m = x[m, t - delay - k] and zero before the first frame (eq. 24), and G (L, M) the
+ * prediction filter: y_t = x_t - G^H xs_t (eq. 26).  X, Y (B, M, F, T), G (B, F, L, M) complex128.
+ * One workgroup per (mixture, bin).  1 <= M <= 8, taps >= 1, taps M <= 64, else
+ * SSSPY_ERR_UNSUPPORTED; delay >= 1 and floor_kind one of SSSPY_FLOOR_*, else SSSPY_ERR_BADARG.
+ * No fp64 atomics: the same bits on every run.  `route`: SSSPY_WPE_ROUTE_AUTO, or
+ * SSSPY_WPE_ROUTE_STREAMING to re-read the slab where it would fit in LDS (the tests compare the
+ * two).  (Added at SSSPY_ABI_VERSION 11 without a bump: no existing argument list changed.) */
+enum {
+  SSSPY_WPE_ROUTE_AUTO = 0,
+  SSSPY_WPE_ROUTE_RESIDENT = 1,  /* the M x T slab of the bin stays in LDS for the whole launch */
+  SSSPY_WPE_ROUTE_STREAMING = 2, /* the slab is re-read from memory in tiles on every walk       */
+};
+
+/* SSSPY_WPE_ROUTE_RESIDENT or _STREAMING for a shape (-1: a shape the kernels do not take);
+ * lds_bytes (may be NULL) receives the dynamic LDS of a workgroup on that route. */
+int ssspy_wpe_route(int B, int M, int F, int T, int taps, int *lds_bytes);
+
+/* n_steps >= 1 iterations on G in place in one launch, each: lambda_t = floor(mean_m |y_mt|^2)
+ * (eq. 45), R = sum_t xs_t xs_t^H / lambda_t and P = sum_t xs_t x_t^H / lambda_t (eq. 46, 47),
+ * G = R^-1 P by a Cholesky factorisation (eq. 48); then Y of the last G when Y is not NULL.
+ * loss_data (may be NULL): (F, slot_stride), slot_stride >= (n_steps + 1) B; iteration s leaves
+ * (1 / T) sum_t [M log lambda_t + sum_m |y_mt|^2 / lambda_t] (the negative log-likelihood of eq. 41
+ * up to a constant) of the state it STARTS from at [f, s B + b] and the last state goes to entry
+ * n_steps; fold the bins with ssspy_fold_scalar_slots.  A pivot that is not positive and finite bumps
+ * info[0] once per (mixture, bin) and ends the iterations of that bin: its G stays what the failing
+ * iteration started from and its Y is formed from that. */
+int ssspy_wpe_steps(const void *X, void *G, void *Y, int B, int M, int F, int T, int taps, int delay,
+                    int floor_kind, double floor_eps, int n_steps, double *loss_data,
+                    long long slot_stride, int *info, int route, void *stream);
+
+/* One iteration (eq. 45 - 48) and Y of the new G.  What the iteration formed is handed out where the
+ * pointer is not NULL: lambda (B, F, T), R (B, F, L, L) as a full Hermitian matrix, P (B, F, L, M)
+ * and the upper-triangular Cholesky factor U (B, F, L, L), R = U^H U, zeros below the diagonal. */
+int ssspy_wpe_step(const void *X, void *G, void *Y, int B, int M, int F, int T, int taps, int delay,
+                   int floor_kind, double floor_eps, int *info, double *lambda, void *R, void *P,
+                   void *U, int route, void *stream);
+
+/* Y = X - G^H xs (eq. 26) for a given G; Y and loss_data (as above with n_steps = 0: one entry per
+ * mixture and bin) may each be NULL, not both. */
+int ssspy_wpe_apply(const void *X, const void *G, void *Y, int B, int M, int F, int T, int taps,
+                    int delay, int floor_kind, double floor_eps, double *loss_data,
+                    long long slot_stride, int route, void *stream);
+
 /* ------------------------------------------------------------------ STFT / ISTFT
  * The transforms the reference's workflow takes from SciPy either side of a separator
  * (tests/package/bss/test_ilrma.py, test_iva.py, test_mnmf.py: scipy.signal.stft(x, window="hann",

@@ -49,6 +49,7 @@ def _units():
         ("fast_iva.hip", "fast_iva.o", []),
         ("overiva.hip", "overiva.o", []),
         ("fdica.hip", "fdica.o", []),
+        ("wpe.hip", "wpe.o", []),
         ("ica.hip", "ica.o", []),
         ("pdsbss.hip", "pdsbss.o", []),
         ("hva.hip", "hva.o", []),

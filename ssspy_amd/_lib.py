@@ -45,6 +45,9 @@ GMNMF_BASIS_REGISTERS, GMNMF_BASIS_LDS_TILE, GMNMF_BASIS_MEMORY = range(3)
 # SSSPY_FDICA_*: `algorithm` of the FDICA entry points; SSSPY_FDICA_ROUTE_*: what ssspy_fdica_route returns
 FDICA_GRAD, FDICA_NATURAL_GRAD, FDICA_AUX_IP1, FDICA_AUX_IP2 = range(4)
 FDICA_ROUTE_RESIDENT, FDICA_ROUTE_STREAMING, FDICA_ROUTE_COMPOSED = range(3)
+# SSSPY_WPE_ROUTE_*: `route` of the WPE entry points and what ssspy_wpe_route returns; the limits
+WPE_ROUTE_AUTO, WPE_ROUTE_RESIDENT, WPE_ROUTE_STREAMING = range(3)
+WPE_MAX_CHANNELS, WPE_MAX_ORDER = 8, 64
 # SSSPY_ICA_*: `kind`, `right` of ssspy_ica_stats and `algorithm` of ssspy_ica_step
 ICA_LAPLACE, ICA_LOGISTIC, ICA_LOGCOSH, ICA_IDENTITY, ICA_GIVEN = range(5)
 ICA_RIGHT_Y, ICA_RIGHT_X = range(2)
@@ -160,6 +163,10 @@ PROTOTYPES = {
     "ssspy_fdica_weight": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _d, _p, _q, _p]),
     "ssspy_fdica_route": (_i, [_i, _i, _i, _i, _i]),
     "ssspy_fdica_steps": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _d, _i, _d, _i, _p, _p, _q, _p, _p]),
+    "ssspy_wpe_route": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]),
+    "ssspy_wpe_steps": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _i, _p, _q, _p, _i, _p]),
+    "ssspy_wpe_step": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _p, _p, _p, _p, _p, _i, _p]),
+    "ssspy_wpe_apply": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _p, _q, _i, _p]),
     "ssspy_ica_chunk_samples": (_i, [_i, _q]),
     "ssspy_ica_workspace_bytes": (_z, [_i, _i, _q]),
     "ssspy_ica_stats": (_i, [_p, _p, _p, _p, _p, _z, _i, _i, _q, _i, _i, _p]),

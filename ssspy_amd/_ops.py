@@ -801,6 +801,80 @@ def fdica_steps(X, W, algorithm, holonomic, step_size, flooring, n_steps, info, 
     return W
 
 
+# --------------------------------------------------------------------------------- WPE
+def _wpe_route_arg():
+    """The `route` argument of the WPE entry points: the slab of a bin in LDS where it fits, unless
+    the route table forces the re-reading walk."""
+    return _lib.WPE_ROUTE_STREAMING if _routes.get("wpe_resident") is False else _lib.WPE_ROUTE_AUTO
+
+
+def wpe_route(B, M, F, T, taps):
+    """(_lib.WPE_ROUTE_RESIDENT or _STREAMING, dynamic LDS bytes of a workgroup).  Host only."""
+    import ctypes
+
+    lds = ctypes.c_int(0)
+    route = int(_L().ssspy_wpe_route(B, M, F, T, int(taps), ctypes.byref(lds)))
+    if route < 0:
+        raise ValueError("wpe_route: a shape the WPE kernels do not take")
+    return route, lds.value
+
+
+def wpe_steps(X, G, taps, delay, flooring, n_steps, info, Y=None, loss_data=None, slot_stride=0):
+    """``n_steps`` whole WPE iterations on G (B, F, taps * M, M) in place in one launch, then
+    Y (B, M, F, T) of the last filter.  ``loss_data`` (F, slot_stride): the per-bin loss terms of
+    the state every iteration starts from and, in entry ``n_steps``, of the last, at [f, s * B + b]."""
+    B, M, F, T = X.shape
+    assert tuple(G.shape) == (B, F, int(taps) * M, M)
+    if Y is None:
+        Y = dv.empty((B, M, F, T), dv.c128, X.device)
+    _lib.check(
+        _L().ssspy_wpe_steps(ptr(X), ptr(G), ptr(Y), B, M, F, T, int(taps), int(delay), flooring[0],
+                             flooring[1], int(n_steps), ptr(loss_data), int(slot_stride), ptr(info),
+                             _wpe_route_arg(), _st()),
+        "wpe_steps",
+    )
+    return Y
+
+
+def wpe_step(X, G, taps, delay, flooring, info, Y=None, want_statistics=False):
+    """One WPE iteration on G in place and Y of the new filter.  With ``want_statistics`` also what
+    the iteration formed: (Y, lambda (B, F, T), R (B, F, L, L), P (B, F, L, M), U (B, F, L, L))."""
+    B, M, F, T = X.shape
+    L = int(taps) * M
+    assert tuple(G.shape) == (B, F, L, M)
+    if Y is None:
+        Y = dv.empty((B, M, F, T), dv.c128, X.device)
+    lam = R = P = U = None
+    if want_statistics:
+        lam = dv.zeros((B, F, T), dv.f64, X.device)
+        R = dv.zeros((B, F, L, L), dv.c128, X.device)
+        P = dv.zeros((B, F, L, M), dv.c128, X.device)
+        U = dv.zeros((B, F, L, L), dv.c128, X.device)
+    _lib.check(
+        _L().ssspy_wpe_step(ptr(X), ptr(G), ptr(Y), B, M, F, T, int(taps), int(delay), flooring[0],
+                            flooring[1], ptr(info), ptr(lam), ptr(R), ptr(P), ptr(U),
+                            _wpe_route_arg(), _st()),
+        "wpe_step",
+    )
+    return (Y, lam, R, P, U) if want_statistics else Y
+
+
+def wpe_apply(X, G, taps, delay, flooring=(_lib.FLOOR_NONE, 0.0), Y=None, loss_data=None,
+              slot_stride=0, want_output=True):
+    """Y = X - G^H xs for a given G (B, F, taps * M, M); ``loss_data`` (F, slot_stride >= B): the
+    per-bin loss terms of that state at [f, b]."""
+    B, M, F, T = X.shape
+    assert tuple(G.shape) == (B, F, int(taps) * M, M)
+    if Y is None and want_output:
+        Y = dv.empty((B, M, F, T), dv.c128, X.device)
+    _lib.check(
+        _L().ssspy_wpe_apply(ptr(X), ptr(G), ptr(Y), B, M, F, T, int(taps), int(delay), flooring[0],
+                             flooring[1], ptr(loss_data), int(slot_stride), _wpe_route_arg(), _st()),
+        "wpe_apply",
+    )
+    return Y
+
+
 # ------------------------------------------------------------------------------ time-domain ICA
 def ica_chunk_samples(N, T):
     """Samples per partial record of the statistics pass (a function of the shape only)."""

@@ -35,6 +35,9 @@ _DEFAULTS = {
     # ssspy_permutation_route allows; False: the NumPy solvers on host copies, one mixture after the
     # other (what 1 or 9..16 sources, flooring callables and overlong frame axes run)
     "device_alignment": True,
+    # WPE keeps the slab of a bin in LDS where ssspy_wpe_route puts it there; False: every walk
+    # re-reads it in tiles (what longer frame axes run)
+    "wpe_resident": True,
 }
 VALUES = dict(_DEFAULTS)  # (tests: monkeypatch.setitem(_routes.VALUES, "implied_filter", False))
 
