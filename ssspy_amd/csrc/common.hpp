@@ -140,6 +140,20 @@ __device__ __forceinline__ void cfms(c128 &acc, c128 a, c128 b) {
   acc.y = fma(-a.x, b.y, acc.y);
   acc.y = fma(-a.y, b.x, acc.y);
 }
+// acc += a * conj(b)   (not cfma(acc, a, cconj(b)): that adds the imaginary terms in the other order)
+__device__ __forceinline__ void cfmac(c128 &acc, c128 a, c128 b) {
+  acc.x = fma(a.x, b.x, acc.x);
+  acc.x = fma(a.y, b.y, acc.x);
+  acc.y = fma(a.y, b.x, acc.y);
+  acc.y = fma(-a.x, b.y, acc.y);
+}
+// acc -= conj(a) * b
+__device__ __forceinline__ void cfmsc(c128 &acc, c128 a, c128 b) {
+  acc.x = fma(-a.x, b.x, acc.x);
+  acc.x = fma(-a.y, b.y, acc.x);
+  acc.y = fma(-a.x, b.y, acc.y);
+  acc.y = fma(a.y, b.x, acc.y);
+}
 __device__ __forceinline__ c128 cscale(c128 a, double s) { return cmake(a.x * s, a.y * s); }
 __device__ __forceinline__ double cabs2(c128 a) { return fma(a.x, a.x, a.y * a.y); }
 __device__ __forceinline__ double cabs1(c128 a) { return fabs(a.x) + fabs(a.y); }
@@ -157,10 +171,10 @@ __device__ __forceinline__ c128 crecip(c128 a) {
 }
 __device__ __forceinline__ c128 cdiv(c128 a, c128 b) { return cmul(a, crecip(b)); }
 // 1 / a by v_rcp_f64 + two Newton steps on |a|^2 (~1 ulp) for the pivots of the row-distributed
-// solvers (k_ip1_rows, k_ip2_rows): those kernels are chains of dependent pivots, and Smith's form
-// above is two IEEE divides (~12 dependent instructions each) and a branch per reciprocal.  For
-// well-scaled arguments only: |a|^2 must neither overflow nor underflow (statistics of spectrograms;
-// the latency form k_ip1_small has used the same since round 3).
+// solvers (RecipFast of rows_lu.hpp: k_ip1_rows, k_ip1_small, k_ip2_rows): those kernels are chains of
+// dependent pivots, and Smith's form above is two IEEE divides (~12 dependent instructions each) and
+// a branch per reciprocal.  For well-scaled arguments only: |a|^2 must neither overflow nor underflow
+// (statistics of spectrograms).
 __device__ __forceinline__ c128 crecip_fast(c128 a) {
   const double m2 = fma(a.x, a.x, a.y * a.y);
   double r = __builtin_amdgcn_rcp(m2);

@@ -14,6 +14,7 @@
 // IP1 sweeps on U_n directly and row n of P = mean_j phi(y) y^H is (w_n U_n) W^H, as in
 // ssspy_iva_grad_step.
 #include "common.hpp"
+#include "rows_lu.hpp"
 
 namespace ssspy {
 
@@ -22,23 +23,6 @@ constexpr int FDICA_THREADS = 256;
 // below a workgroup stays under the 64 KiB of LDS that need no opt-in, and two workgroups fit a CU.
 constexpr int FDICA_X_LDS_BYTES = 48 * 1024;
 constexpr int FDICA_ROUTED_SOURCES = 4;  // (ssspy_fdica_route: above, the per-iteration operators)
-
-template <int N>
-constexpr int fdica_group() {
-  return N <= 2 ? 2 : (N <= 4 ? 4 : 8);
-}
-
-// acc += a * conj(b)
-__device__ __forceinline__ void cfmac(c128 &acc, c128 a, c128 b) {
-  acc.x = fma(a.x, b.x, acc.x);
-  acc.x = fma(a.y, b.y, acc.x);
-  acc.y = fma(a.y, b.x, acc.y);
-  acc.y = fma(-a.x, b.y, acc.y);
-}
-
-__device__ __forceinline__ c128 shfl_c(c128 v, int src, int width) {
-  return cmake(__shfl(v.x, src, width), __shfl(v.y, src, width));
-}
 
 // index of (p, q), p <= q, in the row-major upper triangle of an N x N matrix
 template <int N>
@@ -139,7 +123,7 @@ __global__ __launch_bounds__(FDICA_THREADS) void k_fdica_steps(
     const c128 *__restrict__ X, c128 *W, int B, int F, int T, int algorithm, int holonomic,
     double eta, int floor_kind, double eps, int n_steps, double *loss, double *logdet,
     long long slot_stride, int *info) {
-  constexpr int G = fdica_group<N>();
+  constexpr int G = rows_group<N>();
   constexpr int FL = FDICA_THREADS / G;
   constexpr int NH = N * (N + 1) / 2;
   extern __shared__ c128 Xs[];
@@ -309,6 +293,8 @@ __global__ __launch_bounds__(FDICA_THREADS) void k_fdica_steps(
 #pragma unroll
           for (int c = 0; c < N; ++c) wm[c] = shfl_c(w[c], m, G);
           c128 pm = cmake(0.0, 0.0);
+          // (cfmac, where grad_iva.hip has cfma(., ., cconj(.)): the imaginary terms in the other
+          //  order, different bits)
 #pragma unroll
           for (int c = 0; c < N; ++c) cfmac(pm, t[c], wm[c]);
           if (m == nn) pm = holonomic ? cmake(pm.x - 1.0, pm.y) : cmake(0.0, 0.0);

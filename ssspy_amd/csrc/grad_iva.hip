@@ -5,6 +5,7 @@
 // passes of AuxIVA-IP1 (frame powers, weighted covariance) and the step below instead of IP1; the
 // estimate itself is never formed.  ref: ssspy/bss/iva.py:764-818, :936-988, :2341-2973.
 #include "common.hpp"
+#include "rows_lu.hpp"
 #include "rt_dense.hpp"
 
 namespace ssspy {
@@ -93,6 +94,7 @@ __global__ __launch_bounds__(256) void k_grad_step_rows(c128 *W, const c128 *__r
       for (int c = 0; c < N; ++c) wm[c] = cmake(__shfl(Wr[c].x, m, G), __shfl(Wr[c].y, m, G));
       if (!ready) {
         c128 acc = cmake(0.0, 0.0);
+        // (not cfmac: it adds the imaginary terms in the other order, different bits; fdica.hip has it)
 #pragma unroll
         for (int c = 0; c < N; ++c) cfma(acc, t[c], cconj(wm[c]));
         P[m] = acc;
@@ -261,21 +263,16 @@ __global__ __launch_bounds__(64) void k_grad_step_rt(c128 *W, const c128 *__rest
   }
 }
 
-template <int N>
-constexpr int grad_group() {
-  return N <= 2 ? 2 : (N <= 4 ? 4 : 8);
-}
-
 static int grad_bins_per_block(int N) {
   if (N > SSSPY_MAX_SOURCES) return 64;
-  return 256 / (N <= 2 ? 2 : (N <= 4 ? 4 : 8));
+  return 256 / rows_group_of(N);
 }
 
 template <int N>
 static int launch_grad_step(c128 *W, const c128 *S, int ready, int B, int F, int natural,
                             int holonomic, double eta, int *info, double *logdet,
                             long long logdet_stride, hipStream_t st) {
-  constexpr int G = grad_group<N>();
+  constexpr int G = rows_group<N>();
   const dim3 grid((unsigned)((F + 256 / G - 1) / (256 / G)), (unsigned)B), block(256);
 #define SSSPY_GRAD_STEP(NAT, LD)                                                                  \
   hipLaunchKernelGGL((k_grad_step_rows<N, G, NAT, LD>), grid, block, 0, st, W, S, ready, F,      \

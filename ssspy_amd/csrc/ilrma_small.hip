@@ -353,13 +353,9 @@ __global__ __launch_bounds__(256) void k_activation_small_finalize(double *act,
 // LAPACK's choice; the pivot lane broadcasts its row; back substitution broadcasts one unknown per
 // step).  What a single mixture pays for is the LENGTH of the dependent instruction chain: one lane
 // per bin executes ~5000 dependent fp64 instructions (32 us measured), a quarter of the row
-// arithmetic plus reciprocals by v_rcp_f64 + 2 Newton steps (~1 ulp, fast_tiles.hpp) instead of
+// arithmetic plus reciprocals by v_rcp_f64 + 2 Newton steps (~1 ulp, crecip_fast) instead of
 // IEEE divides leave ~1/4 of that.
-__device__ __forceinline__ c128 crecip_nr(c128 a) {
-  const double inv = rcp_nr(fma(a.x, a.x, a.y * a.y));
-  return cmake(a.x * inv, -a.y * inv);
-}
-
+//
 // Input: the finished covariance U (B, F, N, N, N) (nchunks == 0), or the partial records of the
 // split items of k_wcov_fast, upart[(b * groups + group) * nchunks + ch][rbins][N^3] (TailPlan with
 // no unsplit item: a handful of mixtures), which are summed here instead of by k_wcov_fold.
@@ -488,7 +484,7 @@ __global__ __launch_bounds__(256) void k_ip1_small(c128 *W, const c128 *__restri
       const c128 prhs = cmake(__shfl(rhs.x, bln, G), __shfl(rhs.y, bln, G));
       const c128 piv = prow[k];
       ok = ok && (piv.x != 0.0 || piv.y != 0.0);
-      pinv[k] = crecip_nr(piv);
+      pinv[k] = crecip_fast(piv);
       if (order < 0) {  // still unused: eliminate column k
         const c128 f = cmul(a[k], pinv[k]);
 #pragma unroll

@@ -30,14 +30,6 @@ namespace ssspy {
 #endif
 constexpr double PIVOT_RTOL = 16.0 * 2.220446049250313e-16;
 
-// acc += a * conj(b)
-__device__ __forceinline__ void cfmac(c128 &acc, c128 a, c128 b) {
-  acc.x = fma(a.x, b.x, acc.x);
-  acc.x = fma(a.y, b.y, acc.x);
-  acc.y = fma(a.y, b.x, acc.y);
-  acc.y = fma(-a.x, b.y, acc.y);
-}
-
 // ------------------------------------------------------------------------------- frame power
 // A thread per frame, the filter rows wave-uniform.  grid: (ceil(T / 256), bin chunks, B); chunk c
 // stores its sums to slab c of `dst` ((chunks, B, N, T); r2 itself with one chunk) and

@@ -36,21 +36,6 @@ constexpr int WPE_MAX_ORDER = 64;  // taps * n_channels
 constexpr int WPE_SLAB_LDS_BYTES = 48 * 1024;
 constexpr int WPE_MAX_NPT = (WPE_MAX_ORDER * (WPE_MAX_ORDER + 1) / 2 + WPE_THREADS - 1) / WPE_THREADS;
 
-// acc += a * conj(b)
-__device__ __forceinline__ void wpe_cfmac(c128 &acc, c128 a, c128 b) {
-  acc.x = fma(a.x, b.x, acc.x);
-  acc.x = fma(a.y, b.y, acc.x);
-  acc.y = fma(a.y, b.x, acc.y);
-  acc.y = fma(-a.x, b.y, acc.y);
-}
-// acc -= conj(a) * b
-__device__ __forceinline__ void wpe_cfmsc(c128 &acc, c128 a, c128 b) {
-  acc.x = fma(-a.x, b.x, acc.x);
-  acc.x = fma(-a.y, b.y, acc.x);
-  acc.y = fma(-a.x, b.y, acc.y);
-  acc.y = fma(a.y, b.x, acc.y);
-}
-
 // index of (p, q), p <= q, in the row-major upper triangle of an L x L matrix
 __device__ __forceinline__ int wpe_tri(int L, int p, int q) {
   return p * L - p * (p - 1) / 2 + (q - p);
@@ -88,7 +73,7 @@ __device__ __forceinline__ void wpe_frame(const c128 *H, int HS, const c128 *C, 
         const c128 x = H[m * HS + tt - k];
         const c128 *g = Gs + (k * M + m) * M;
 #pragma unroll
-        for (int c = 0; c < M; ++c) wpe_cfmsc(y[c], g[c], x);  // y_c -= conj(G[l, c]) xs[l]
+        for (int c = 0; c < M; ++c) cfmsc(y[c], g[c], x);  // y_c -= conj(G[l, c]) xs[l]
       }
     }
   }
@@ -230,10 +215,10 @@ __global__ __launch_bounds__(WPE_THREADS) void k_wpe(
           const double w = rlam[tt];
 #pragma unroll
           for (int i = 0; i < NPT; ++i)
-            wpe_cfmac(acc[i], cscale(Hb[op[i] + tt], w), Hb[oq[i] + tt]);
+            cfmac(acc[i], cscale(Hb[op[i] + tt], w), Hb[oq[i] + tt]);
 #pragma unroll
           for (int i = 0; i < 2; ++i)
-            wpe_cfmac(accp[i], cscale(Hb[pl[i] + tt], w), Cb[pc[i] + tt]);
+            cfmac(accp[i], cscale(Hb[pl[i] + tt], w), Cb[pc[i] + tt]);
         }
         __syncthreads();  // rlam is rewritten by the next tile
       }
@@ -290,7 +275,7 @@ __global__ __launch_bounds__(WPE_THREADS) void k_wpe(
       for (int k = j + 1 + ty; k < L; k += 16) {
         const c128 ujk = Rs[rj + k - j];
         const int rk = wpe_tri(L, k, k);
-        for (int i = k + tx; i < L; i += 16) wpe_cfmsc(Rs[rk + i - k], ujk, Rs[rj + i - j]);
+        for (int i = k + tx; i < L; i += 16) cfmsc(Rs[rk + i - k], ujk, Rs[rj + i - j]);
       }
       __syncthreads();
     }
@@ -321,7 +306,7 @@ __global__ __launch_bounds__(WPE_THREADS) void k_wpe(
 #pragma unroll
       for (int i = 0; i < 2; ++i)
         if (row[i] > j)
-          wpe_cfmsc(Ps[row[i] * M + col[i]], Rs[rj + row[i] - j], cscale(Ps[j * M + col[i]], invd[j]));
+          cfmsc(Ps[row[i] * M + col[i]], Rs[rj + row[i] - j], cscale(Ps[j * M + col[i]], invd[j]));
       __syncthreads();
     }
 #pragma unroll

@@ -223,8 +223,11 @@ def test_ten_steps_in_one_launch_equal_ten_launches_bitwise(form, shape):
 
 
 # 5
-@pytest.mark.parametrize("T", [37, 700], ids=["t37", "t700"])
-@pytest.mark.parametrize("N", list(range(2, 9)))
+# (T = 700 is slab resident up to 4 sources; 1600 / 1100 / 800 frames are the re-reading form there)
+STEP_SHAPES = [(N, T) for N in range(2, 9) for T in (37, 700)] + [(2, 1600), (3, 1100), (4, 800)]
+
+
+@pytest.mark.parametrize("N,T", STEP_SHAPES, ids=["{}-t{}".format(*s) for s in STEP_SHAPES])
 def test_steps_operator_against_numpy(N, T):
     from ssspy_amd import _lib
 

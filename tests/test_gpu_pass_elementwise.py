@@ -561,7 +561,8 @@ def test_ilrma_normalize(N, flooring):
             check("ilrma_normalize_output_tracked_logdet", "N={}".format(N), ol.get(), res[4], res[5])
 
 
-@pytest.mark.parametrize("B,N", [(2, 2), (2, 3), (2, 4), (40, 4), (2, 6), (2, 8), (2, 9), (1, 16)])
+@pytest.mark.parametrize("B,N", [(2, 2), (2, 3), (2, 4), (40, 4), (2, 5), (2, 6), (2, 7), (2, 8), (2, 9),
+                                 (1, 16)])
 def test_update_by_ip1(B, N):
     """update_by_ip1 and update_by_ip1_logdet (shares folded with fold_scalar_slots): normwise per
     bin, c = 8 x what np.linalg.solve makes of the same inputs (see the module docstring)."""
