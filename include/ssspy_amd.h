@@ -1592,6 +1592,71 @@ int ssspy_wpe_apply(const void *X, const void *G, void *Y, int B, int M, int F, 
                     int delay, int floor_kind, double floor_eps, double *loss_data,
                     long long slot_stride, int route, void *stream);
 
+/* ------------------------------------------------------------------ mask-based beamformers
+ * (csrc/beamform.hip)  Masks as covariance weights (Higuchi et al., ICASSP 2016; Heymann et al.,
+ * ICASSP 2016).  Per (mixture, bin), with x_t the M channels of frame t, m_nt >= 0 the mask of source
+ * n and u_nt its noise weight -- noise_mask (B, N, F, T), or (B, F, T) shared by the sources when
+ * noise_shared, or 1 - m_nt formed by the kernel when noise_mask is NULL (never total minus signal):
+ *   S_n = sum_t m_nt x_t x_t^H, a_n = sum_t m_nt, N_n = sum_t u_nt x_t x_t^H, b_n = sum_t u_nt
+ *   Phi_s = S_n / max(a_n, 1e-10)
+ *   Phi_v = N_n / max(b_n, 1e-10) + diagonal_loading (tr(N_n / max(b_n, 1e-10)) / M) I
+ * X (B, M, F, T) and Y (B, N, F, T) complex128, masks float64, W (B, F, N, M) complex128 with row n
+ * the filter w_n^H (Y = W X per bin), covariances (B, F, N, M, M) complex128 as full Hermitian
+ * matrices, a and b (B, F, N) float64.  One workgroup per (mixture, bin); every sum is formed in frame
+ * order by one thread: no fp64 atomics, the same bits on every run and on both routes.
+ * 1 <= M <= 8 and 1 <= N <= 16, else SSSPY_ERR_UNSUPPORTED.
+ * (Added at SSSPY_ABI_VERSION 11 without a bump, as the WPE entry points were: no existing argument
+ * list changed.) */
+enum {
+  SSSPY_BEAMFORM_MVDR = 0,          /* Souden, Benesty, Affes, IEEE TASLP 18(2), 2010, eq. 18        */
+  SSSPY_BEAMFORM_GEV_REFERENCE = 1, /* Warsitz, Haeb-Umbach, IEEE TASLP 15(5), 2007, eq. 12, scaled  */
+                                    /* to be distortionless towards the reference channel            */
+  SSSPY_BEAMFORM_GEV_BAN = 2,       /* the same with blind analytic normalisation (eq. 30)           */
+  SSSPY_BEAMFORM_MWF = 3,           /* speech-distortion-weighted MWF (Souden 2010, eq. 16; Doclo)   */
+};
+enum {
+  SSSPY_BEAMFORM_ROUTE_AUTO = 0,
+  SSSPY_BEAMFORM_ROUTE_RESIDENT = 1,  /* the M x T slab of the bin stays in LDS: X is read once     */
+  SSSPY_BEAMFORM_ROUTE_STREAMING = 2, /* the slab is re-read in tiles for the apply walk            */
+};
+
+/* SSSPY_BEAMFORM_ROUTE_RESIDENT (16 M T <= 48 KiB) or _STREAMING for a shape (-1: a shape the kernel
+ * does not take); lds_bytes (may be NULL) receives the dynamic LDS of a workgroup of
+ * ssspy_beamform_run on that route. */
+int ssspy_beamform_route(int B, int M, int N, int F, int T, int *lds_bytes);
+
+/* The sums alone: S <- S_n, Nv <- N_n, a <- a_n, b <- b_n; with normalize, S <- S_n / max(a_n, 1e-10)
+ * and Nv <- N_n / max(b_n, 1e-10) (no loading), the division ssspy_beamform_run makes. */
+int ssspy_beamform_covariances(const void *X, const double *mask, const double *noise_mask,
+                               int noise_shared, void *S, void *Nv, double *a, double *b, int B,
+                               int M, int N, int F, int T, int normalize, void *stream);
+
+/* W from given Phi_s and Phi_v (loading included), `kind` one of SSSPY_BEAMFORM_*:
+ *   MVDR  A = Phi_v^-1 Phi_s by a Cholesky factorisation, w = A e_ref / max(Re tr A, 1e-10)
+ *         (Souden 2010, eq. 18)
+ *   MWF   w = (Phi_s + mu Phi_v)^-1 Phi_s e_ref, mu > 0 (Souden 2010, eq. 16)
+ *   GEV   Phi_v = L L^H, C = L^-1 Phi_s L^-H, v the unit eigenvector of its largest eigenvalue
+ *         (Hermitian Jacobi), w0 = L^-H v (Warsitz 2007, eq. 12), a = L v = Phi_v w0;
+ *         _REFERENCE: w = w0 conj(a_ref); _BAN: w = w0 p ||a|| / sqrt(M), p = conj(a_ref) / |a_ref|
+ *         (1 where a_ref = 0) -- eq. 30 with the phase pinned.  Both are invariant under the phase of v.
+ * A Phi_s that is zero in every entry gives w = 0.  A Cholesky pivot that is not positive and finite
+ * bumps info[0] (may be NULL) once per (mixture, bin, source), and that source gets w = 0. */
+int ssspy_beamform_filter(const void *Phi_s, const void *Phi_v, void *W, int B, int M, int N, int F,
+                          int kind, int reference_id, double mu, int *info, void *stream);
+
+/* Everything in one launch: the sums, Phi_s and Phi_v, the filters of ssspy_beamform_filter and
+ * y_nt = w_n^H x_t.  W, Y and the pair Phi_s, Phi_v may each be NULL (not all): what is NULL is not
+ * written.  `route`: SSSPY_BEAMFORM_ROUTE_AUTO, or _STREAMING to re-read the slab where it would fit
+ * in LDS (the tests compare the two). */
+int ssspy_beamform_run(const void *X, const double *mask, const double *noise_mask, int noise_shared,
+                       void *W, void *Y, void *Phi_s, void *Phi_v, int B, int M, int N, int F, int T,
+                       int kind, int reference_id, double diagonal_loading, double mu, int *info,
+                       int route, void *stream);
+
+/* Y = W X per bin for given filters W (B, F, N, M): the apply walk of ssspy_beamform_run. */
+int ssspy_beamform_apply(const void *X, const void *W, void *Y, int B, int M, int N, int F, int T,
+                         void *stream);
+
 /* ------------------------------------------------------------------ STFT / ISTFT
  * The transforms the reference's workflow takes from SciPy either side of a separator
  * (tests/package/bss/test_ilrma.py, test_iva.py, test_mnmf.py: scipy.signal.stft(x, window="hann",

@@ -50,6 +50,7 @@ def _units():
         ("overiva.hip", "overiva.o", []),
         ("fdica.hip", "fdica.o", []),
         ("wpe.hip", "wpe.o", []),
+        ("beamform.hip", "beamform.o", []),
         ("ica.hip", "ica.o", []),
         ("pdsbss.hip", "pdsbss.o", []),
         ("hva.hip", "hva.o", []),

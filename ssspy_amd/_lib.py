@@ -48,6 +48,11 @@ FDICA_ROUTE_RESIDENT, FDICA_ROUTE_STREAMING, FDICA_ROUTE_COMPOSED = range(3)
 # SSSPY_WPE_ROUTE_*: `route` of the WPE entry points and what ssspy_wpe_route returns; the limits
 WPE_ROUTE_AUTO, WPE_ROUTE_RESIDENT, WPE_ROUTE_STREAMING = range(3)
 WPE_MAX_CHANNELS, WPE_MAX_ORDER = 8, 64
+# SSSPY_BEAMFORM_*: `kind` of the beamformer entry points; SSSPY_BEAMFORM_ROUTE_*: their `route` and
+# what ssspy_beamform_route returns; the limits
+BEAMFORM_MVDR, BEAMFORM_GEV_REFERENCE, BEAMFORM_GEV_BAN, BEAMFORM_MWF = range(4)
+BEAMFORM_ROUTE_AUTO, BEAMFORM_ROUTE_RESIDENT, BEAMFORM_ROUTE_STREAMING = range(3)
+BEAMFORM_MAX_CHANNELS, BEAMFORM_MAX_SOURCES = 8, 16
 # SSSPY_ICA_*: `kind`, `right` of ssspy_ica_stats and `algorithm` of ssspy_ica_step
 ICA_LAPLACE, ICA_LOGISTIC, ICA_LOGCOSH, ICA_IDENTITY, ICA_GIVEN = range(5)
 ICA_RIGHT_Y, ICA_RIGHT_X = range(2)
@@ -167,6 +172,12 @@ PROTOTYPES = {
     "ssspy_wpe_steps": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _i, _p, _q, _p, _i, _p]),
     "ssspy_wpe_step": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _p, _p, _p, _p, _p, _i, _p]),
     "ssspy_wpe_apply": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _p, _q, _i, _p]),
+    "ssspy_beamform_route": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]),
+    "ssspy_beamform_covariances": (_i, [_p, _p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "ssspy_beamform_filter": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _d, _p, _p]),
+    "ssspy_beamform_run": (_i, [_p, _p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _d, _p,
+                                _i, _p]),
+    "ssspy_beamform_apply": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "ssspy_ica_chunk_samples": (_i, [_i, _q]),
     "ssspy_ica_workspace_bytes": (_z, [_i, _i, _q]),
     "ssspy_ica_stats": (_i, [_p, _p, _p, _p, _p, _z, _i, _i, _q, _i, _i, _p]),

@@ -875,6 +875,101 @@ def wpe_apply(X, G, taps, delay, flooring=(_lib.FLOOR_NONE, 0.0), Y=None, loss_d
     return Y
 
 
+# ------------------------------------------------------------------- mask-based beamformers
+def _beamform_route_arg():
+    """The `route` argument of ssspy_beamform_run: the slab of a bin in LDS where it fits, unless the
+    route table forces the re-reading walk."""
+    return (_lib.BEAMFORM_ROUTE_STREAMING if _routes.get("beamform_resident") is False
+            else _lib.BEAMFORM_ROUTE_AUTO)
+
+
+def beamform_route(B, M, N, F, T):
+    """(_lib.BEAMFORM_ROUTE_RESIDENT or _STREAMING, dynamic LDS bytes of a workgroup).  Host only."""
+    import ctypes
+
+    lds = ctypes.c_int(0)
+    route = int(_L().ssspy_beamform_route(B, M, N, F, T, ctypes.byref(lds)))
+    if route < 0:
+        raise ValueError("beamform_route: a shape the beamformer kernel does not take")
+    return route, lds.value
+
+
+def _beamform_masks(X, mask, noise_mask):
+    """(B, M, N, F, T, noise_shared) after checking the layouts of the masks against X."""
+    B, M, F, T = X.shape
+    N = mask.shape[1]
+    assert tuple(mask.shape) == (B, N, F, T) and mask.dtype == dv.f64
+    shared = False
+    if noise_mask is not None:
+        assert noise_mask.dtype == dv.f64
+        shared = noise_mask.dim() == 3
+        assert tuple(noise_mask.shape) == ((B, F, T) if shared else (B, N, F, T))
+    return B, M, N, F, T, shared
+
+
+def beamform_covariances(X, mask, noise_mask=None, normalize=False):
+    """(S, Nv (B, F, N, M, M), a, b (B, F, N)): the mask-weighted sums of x x^H and of the weights;
+    with ``normalize`` S and Nv divided by max(a, eps) and max(b, eps)."""
+    B, M, N, F, T, shared = _beamform_masks(X, mask, noise_mask)
+    S = dv.empty((B, F, N, M, M), dv.c128, X.device)
+    Nv = dv.empty((B, F, N, M, M), dv.c128, X.device)
+    a = dv.empty((B, F, N), dv.f64, X.device)
+    b = dv.empty((B, F, N), dv.f64, X.device)
+    _lib.check(
+        _L().ssspy_beamform_covariances(ptr(X), ptr(mask), ptr(noise_mask), int(shared), ptr(S),
+                                        ptr(Nv), ptr(a), ptr(b), B, M, N, F, T, int(bool(normalize)),
+                                        _st()),
+        "beamform_covariances",
+    )
+    return S, Nv, a, b
+
+
+def beamform_filter(Phi_s, Phi_v, kind, reference_id, mu=1.0, info=None):
+    """W (B, F, N, M), rows w_n^H, from given covariances (B, F, N, M, M)."""
+    B, F, N, M = Phi_s.shape[:4]
+    assert tuple(Phi_s.shape) == (B, F, N, M, M) and tuple(Phi_v.shape) == (B, F, N, M, M)
+    W = dv.empty((B, F, N, M), dv.c128, Phi_s.device)
+    _lib.check(
+        _L().ssspy_beamform_filter(ptr(Phi_s), ptr(Phi_v), ptr(W), B, M, N, F, int(kind),
+                                   int(reference_id), float(mu), ptr(info), _st()),
+        "beamform_filter",
+    )
+    return W
+
+
+def beamform_run(X, mask, noise_mask, kind, reference_id, diagonal_loading, mu, info=None,
+                 want_output=True, want_covariances=False):
+    """One launch from X and the masks to the filters and Y: (W (B, F, N, M), Y (B, N, F, T) or None,
+    Phi_s, Phi_v (B, F, N, M, M) or None)."""
+    B, M, N, F, T, shared = _beamform_masks(X, mask, noise_mask)
+    W = dv.empty((B, F, N, M), dv.c128, X.device)
+    Y = dv.empty((B, N, F, T), dv.c128, X.device) if want_output else None
+    Ps = Pv = None
+    if want_covariances:
+        Ps = dv.empty((B, F, N, M, M), dv.c128, X.device)
+        Pv = dv.empty((B, F, N, M, M), dv.c128, X.device)
+    _lib.check(
+        _L().ssspy_beamform_run(ptr(X), ptr(mask), ptr(noise_mask), int(shared), ptr(W), ptr(Y),
+                                ptr(Ps), ptr(Pv), B, M, N, F, T, int(kind), int(reference_id),
+                                float(diagonal_loading), float(mu), ptr(info), _beamform_route_arg(),
+                                _st()),
+        "beamform_run",
+    )
+    return W, Y, Ps, Pv
+
+
+def beamform_apply(X, W, Y=None):
+    """Y (B, N, F, T) = W X per bin for filters W (B, F, N, M)."""
+    B, M, F, T = X.shape
+    N = W.shape[2]
+    assert tuple(W.shape) == (B, F, N, M)
+    if Y is None:
+        Y = dv.empty((B, N, F, T), dv.c128, X.device)
+    _lib.check(_L().ssspy_beamform_apply(ptr(X), ptr(W), ptr(Y), B, M, N, F, T, _st()),
+               "beamform_apply")
+    return Y
+
+
 # ------------------------------------------------------------------------------ time-domain ICA
 def ica_chunk_samples(N, T):
     """Samples per partial record of the statistics pass (a function of the shape only)."""

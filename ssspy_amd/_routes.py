@@ -38,6 +38,9 @@ _DEFAULTS = {
     # WPE keeps the slab of a bin in LDS where ssspy_wpe_route puts it there; False: every walk
     # re-reads it in tiles (what longer frame axes run)
     "wpe_resident": True,
+    # the beamformers keep the slab of a bin in LDS where ssspy_beamform_route puts it there; False:
+    # the apply walk re-reads it in tiles (what longer frame axes run)
+    "beamform_resident": True,
 }
 VALUES = dict(_DEFAULTS)  # (tests: monkeypatch.setitem(_routes.VALUES, "implied_filter", False))
 
