@@ -1657,6 +1657,64 @@ int ssspy_beamform_run(const void *X, const double *mask, const double *noise_ma
 int ssspy_beamform_apply(const void *X, const void *W, void *Y, int B, int M, int N, int F, int T,
                          void *stream);
 
+/* ------------------------------------------------------------------ WPD (csrc/wpd.hip)
+ * The convolutional beamformer (weighted power minimisation distortionless response): Nakatani,
+ * Kinoshita, IEEE SPL 26(6), 2019; Boeddeker et al., ICASSP 2020 for the form without a steering
+ * vector.  Per (mixture, bin, source), with x_t the M channels of frame t and Lb = (taps + 1) M: the
+ * stacked vector xb_t in C^Lb has block 0 = x_t and block j = 1..taps = x_{t - delay - (j - 1)}, zero
+ * before the first frame; the filter wb in C^Lb gives y_t = wb^H xb_t.  X (B, M, F, T), Y (B, N, F, T)
+ * and W (B, F, N, Lb) complex128, W[l] = conj(wb[l]) (Y = W xb per bin); mask (B, N, F, T) float64;
+ * steering (B, F, N, M) complex128.  One workgroup per (mixture, bin, source); every sum is formed in
+ * frame order by one thread: no fp64 atomics, the same bits on every run and on both routes.
+ * 1 <= M <= 8, taps >= 0, (taps + 1) M <= 64 and 1 <= N <= 16, else SSSPY_ERR_UNSUPPORTED; delay >= 1
+ * and floor_kind one of SSSPY_FLOOR_*, else SSSPY_ERR_BADARG.  `route`: SSSPY_WPD_ROUTE_AUTO, or
+ * SSSPY_WPD_ROUTE_STREAMING to re-read the slab where it would fit in LDS (the tests compare the
+ * two).  (Added at SSSPY_ABI_VERSION 11 without a bump, as the WPE and beamformer entry points were:
+ * no existing argument list changed.) */
+enum {
+  SSSPY_WPD_ROUTE_AUTO = 0,
+  SSSPY_WPD_ROUTE_RESIDENT = 1,  /* the M x T slab of the bin stays in LDS for the whole launch */
+  SSSPY_WPD_ROUTE_STREAMING = 2, /* the slab is re-read from memory in tiles on every walk       */
+};
+
+/* SSSPY_WPD_ROUTE_RESIDENT (16 M (T + max(taps - 1, 0)) <= 48 KiB) or _STREAMING for a shape (-1: a
+ * shape the kernels do not take); lds_bytes (may be NULL) receives the dynamic LDS of a workgroup on
+ * that route. */
+int ssspy_wpd_route(int B, int M, int N, int F, int T, int taps, int *lds_bytes);
+
+/* n_steps >= 1 iterations on W in place in one launch, each: lambda_t = floor(|y_t|^2),
+ * R = (1 / T) sum_t xb_t xb_t^H / lambda_t + diagonal_loading (tr R / Lb) I, R = U^H U (Cholesky), and
+ *   mask form (steering == NULL): Phi_s = sum_t m_t x_t x_t^H / max(sum_t m_t, 1e-10), summed in the
+ *     first walk; A = (R^-1)[:, :M] Phi_s; wb = A[:, ref] / Re tr(A[:M, :])
+ *   steering form (mask may be NULL): vb = [v; 0], a = R^-1 vb, wb = a conj(v_ref) / (vb^H a)
+ * with wb = 0 where the denominator is zero or not finite (an all-zero mask); then Y of the last W
+ * when Y is not NULL.  Phi_s (may be NULL; mask form) receives (B, F, N, M, M), full Hermitian.
+ * loss_data (may be NULL): (F N, slot_stride), slot_stride >= (n_steps + 1) B; iteration s leaves
+ * (1 / T) sum_t [log lambda_t + |y_t|^2 / lambda_t] of the state it STARTS from at
+ * [f N + n, s B + b] and the last state goes to entry n_steps; fold the rows with
+ * ssspy_fold_scalar_slots.  A pivot that is not positive and finite bumps info[0] once per (mixture,
+ * bin, source) and ends the iterations of that triple: its W stays what the failing iteration started
+ * from, its Y is formed from that, and the loss term of that kept state fills every entry behind the
+ * failing iteration's (s + 1 .. n_steps). */
+int ssspy_wpd_steps(const void *X, const double *mask, const void *steering, void *W, void *Phi_s,
+                    void *Y, int B, int M, int N, int F, int T, int taps, int delay, int reference_id,
+                    double diagonal_loading, int floor_kind, double floor_eps, int n_steps,
+                    double *loss_data, long long slot_stride, int *info, int route, void *stream);
+
+/* One iteration and Y of the new W.  What the iteration formed is handed out where the pointer is not
+ * NULL: lambda (B, F, N, T), R (B, F, N, Lb, Lb) as a full Hermitian matrix (loading included), Phi_s
+ * and the upper-triangular Cholesky factor U (B, F, N, Lb, Lb), R = U^H U, zeros below the diagonal. */
+int ssspy_wpd_step(const void *X, const double *mask, const void *steering, void *W, void *Phi_s,
+                   void *Y, int B, int M, int N, int F, int T, int taps, int delay, int reference_id,
+                   double diagonal_loading, int floor_kind, double floor_eps, int *info,
+                   double *lambda, void *R, void *U, int route, void *stream);
+
+/* Y = W xb for given filters; Y and loss_data (as above with n_steps = 0: one entry per mixture, bin
+ * and source) may each be NULL, not both. */
+int ssspy_wpd_apply(const void *X, const void *W, void *Y, int B, int M, int N, int F, int T, int taps,
+                    int delay, int floor_kind, double floor_eps, double *loss_data,
+                    long long slot_stride, int route, void *stream);
+
 /* ------------------------------------------------------------------ STFT / ISTFT
  * The transforms the reference's workflow takes from SciPy either side of a separator
  * (tests/package/bss/test_ilrma.py, test_iva.py, test_mnmf.py: scipy.signal.stft(x, window="hann",

@@ -51,6 +51,7 @@ def _units():
         ("fdica.hip", "fdica.o", []),
         ("wpe.hip", "wpe.o", []),
         ("beamform.hip", "beamform.o", []),
+        ("wpd.hip", "wpd.o", []),
         ("ica.hip", "ica.o", []),
         ("pdsbss.hip", "pdsbss.o", []),
         ("hva.hip", "hva.o", []),

@@ -53,6 +53,10 @@ WPE_MAX_CHANNELS, WPE_MAX_ORDER = 8, 64
 BEAMFORM_MVDR, BEAMFORM_GEV_REFERENCE, BEAMFORM_GEV_BAN, BEAMFORM_MWF = range(4)
 BEAMFORM_ROUTE_AUTO, BEAMFORM_ROUTE_RESIDENT, BEAMFORM_ROUTE_STREAMING = range(3)
 BEAMFORM_MAX_CHANNELS, BEAMFORM_MAX_SOURCES = 8, 16
+# SSSPY_WPD_ROUTE_*: `route` of the WPD entry points and what ssspy_wpd_route returns; the limits
+# ((taps + 1) * n_channels <= WPD_MAX_ORDER)
+WPD_ROUTE_AUTO, WPD_ROUTE_RESIDENT, WPD_ROUTE_STREAMING = range(3)
+WPD_MAX_CHANNELS, WPD_MAX_ORDER, WPD_MAX_SOURCES = 8, 64, 16
 # SSSPY_ICA_*: `kind`, `right` of ssspy_ica_stats and `algorithm` of ssspy_ica_step
 ICA_LAPLACE, ICA_LOGISTIC, ICA_LOGCOSH, ICA_IDENTITY, ICA_GIVEN = range(5)
 ICA_RIGHT_Y, ICA_RIGHT_X = range(2)
@@ -178,6 +182,12 @@ PROTOTYPES = {
     "ssspy_beamform_run": (_i, [_p, _p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _d, _p,
                                 _i, _p]),
     "ssspy_beamform_apply": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "ssspy_wpd_route": (_i, [_i, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]),
+    "ssspy_wpd_steps": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _d, _i, _d, _i, _p,
+                             _q, _p, _i, _p]),
+    "ssspy_wpd_step": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _d, _i, _d, _p, _p,
+                            _p, _p, _i, _p]),
+    "ssspy_wpd_apply": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _d, _p, _q, _i, _p]),
     "ssspy_ica_chunk_samples": (_i, [_i, _q]),
     "ssspy_ica_workspace_bytes": (_z, [_i, _i, _q]),
     "ssspy_ica_stats": (_i, [_p, _p, _p, _p, _p, _z, _i, _i, _q, _i, _i, _p]),

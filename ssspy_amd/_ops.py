@@ -970,6 +970,94 @@ def beamform_apply(X, W, Y=None):
     return Y
 
 
+# --------------------------------------------------------------------------------- WPD
+def _wpd_route_arg():
+    """The `route` argument of the WPD entry points: the slab of a bin in LDS where it fits, unless
+    the route table forces the re-reading walk."""
+    return _lib.WPD_ROUTE_STREAMING if _routes.get("wpd_resident") is False else _lib.WPD_ROUTE_AUTO
+
+
+def wpd_route(B, M, N, F, T, taps):
+    """(_lib.WPD_ROUTE_RESIDENT or _STREAMING, dynamic LDS bytes of a workgroup).  Host only."""
+    import ctypes
+
+    lds = ctypes.c_int(0)
+    route = int(_L().ssspy_wpd_route(B, M, N, F, T, int(taps), ctypes.byref(lds)))
+    if route < 0:
+        raise ValueError("wpd_route: a shape the WPD kernel does not take")
+    return route, lds.value
+
+
+def _wpd_operands(X, mask, steering, W, taps):
+    """(B, M, N, F, T) after checking the layouts of the masks, the steering vectors and W against X."""
+    B, M, F, T = X.shape
+    N = W.shape[2]
+    assert tuple(W.shape) == (B, F, N, (int(taps) + 1) * M)
+    assert mask is None or (tuple(mask.shape) == (B, N, F, T) and mask.dtype == dv.f64)
+    assert steering is None or tuple(steering.shape) == (B, F, N, M)
+    return B, M, N, F, T
+
+
+def wpd_steps(X, mask, steering, W, taps, delay, reference_id, diagonal_loading, flooring, n_steps,
+              info, Y=None, Phi_s=None, loss_data=None, slot_stride=0):
+    """``n_steps`` whole WPD iterations on W (B, F, N, (taps + 1) M) in place in one launch, then
+    Y (B, N, F, T) of the last filter.  ``loss_data`` (F N, slot_stride): the per-(bin, source) loss
+    terms of the state every iteration starts from and, in entry ``n_steps``, of the last, at
+    [f N + n, s * B + b]."""
+    B, M, N, F, T = _wpd_operands(X, mask, steering, W, taps)
+    if Y is None:
+        Y = dv.empty((B, N, F, T), dv.c128, X.device)
+    _lib.check(
+        _L().ssspy_wpd_steps(ptr(X), ptr(mask), ptr(steering), ptr(W), ptr(Phi_s), ptr(Y), B, M, N, F,
+                             T, int(taps), int(delay), int(reference_id), float(diagonal_loading),
+                             flooring[0], flooring[1], int(n_steps), ptr(loss_data), int(slot_stride),
+                             ptr(info), _wpd_route_arg(), _st()),
+        "wpd_steps",
+    )
+    return Y
+
+
+def wpd_step(X, mask, steering, W, taps, delay, reference_id, diagonal_loading, flooring, info,
+             Y=None, Phi_s=None, want_statistics=False):
+    """One WPD iteration on W in place and Y of the new filter.  With ``want_statistics`` also what the
+    iteration formed: (Y, lambda (B, F, N, T), R (B, F, N, Lb, Lb), Phi_s (B, F, N, M, M),
+    U (B, F, N, Lb, Lb))."""
+    B, M, N, F, T = _wpd_operands(X, mask, steering, W, taps)
+    Lb = (int(taps) + 1) * M
+    if Y is None:
+        Y = dv.empty((B, N, F, T), dv.c128, X.device)
+    lam = R = U = None
+    if want_statistics:
+        lam = dv.zeros((B, F, N, T), dv.f64, X.device)
+        R = dv.zeros((B, F, N, Lb, Lb), dv.c128, X.device)
+        U = dv.zeros((B, F, N, Lb, Lb), dv.c128, X.device)
+        if Phi_s is None:
+            Phi_s = dv.zeros((B, F, N, M, M), dv.c128, X.device)
+    _lib.check(
+        _L().ssspy_wpd_step(ptr(X), ptr(mask), ptr(steering), ptr(W), ptr(Phi_s), ptr(Y), B, M, N, F, T,
+                            int(taps), int(delay), int(reference_id), float(diagonal_loading),
+                            flooring[0], flooring[1], ptr(info), ptr(lam), ptr(R), ptr(U),
+                            _wpd_route_arg(), _st()),
+        "wpd_step",
+    )
+    return (Y, lam, R, Phi_s, U) if want_statistics else Y
+
+
+def wpd_apply(X, W, taps, delay, flooring=(_lib.FLOOR_NONE, 0.0), Y=None, loss_data=None,
+              slot_stride=0, want_output=True):
+    """Y (B, N, F, T) = W xb for given filters W (B, F, N, (taps + 1) M); ``loss_data``
+    (F N, slot_stride >= B): the per-(bin, source) loss terms of that state at [f N + n, b]."""
+    B, M, N, F, T = _wpd_operands(X, None, None, W, taps)
+    if Y is None and want_output:
+        Y = dv.empty((B, N, F, T), dv.c128, X.device)
+    _lib.check(
+        _L().ssspy_wpd_apply(ptr(X), ptr(W), ptr(Y), B, M, N, F, T, int(taps), int(delay), flooring[0],
+                             flooring[1], ptr(loss_data), int(slot_stride), _wpd_route_arg(), _st()),
+        "wpd_apply",
+    )
+    return Y
+
+
 # ------------------------------------------------------------------------------ time-domain ICA
 def ica_chunk_samples(N, T):
     """Samples per partial record of the statistics pass (a function of the shape only)."""

@@ -41,6 +41,9 @@ _DEFAULTS = {
     # the beamformers keep the slab of a bin in LDS where ssspy_beamform_route puts it there; False:
     # the apply walk re-reads it in tiles (what longer frame axes run)
     "beamform_resident": True,
+    # WPD keeps the slab of a bin in LDS where ssspy_wpd_route puts it there; False: every walk
+    # re-reads it in tiles (what longer frame axes run)
+    "wpd_resident": True,
 }
 VALUES = dict(_DEFAULTS)  # (tests: monkeypatch.setitem(_routes.VALUES, "implied_filter", False))
 
