@@ -1715,6 +1715,54 @@ int ssspy_wpd_apply(const void *X, const void *W, void *Y, int B, int M, int N, 
                     int delay, int floor_kind, double floor_eps, double *loss_data,
                     long long slot_stride, int route, void *stream);
 
+/* ------------------------------------------------------------------ ConvIVA (csrc/conviva.hip)
+ * IVA with joint dereverberation (convolutional AuxIVA): Nakatani et al., Interspeech 2020 (the
+ * source-wise factorisation); Ikeshita et al., WASPAA 2019.  As many sources as channels, N = M.  With
+ * xb_t, Lb and W (B, F, N, Lb) as for WPD above, L = taps M and phi (B, N, T) float64 the auxiliary
+ * weights of the sources (ssspy_iva_weight on the frame powers of the estimate), per (mixture, bin,
+ * source): Rb = (1 / T) sum_t phi_t xb_t xb_t^H, C = Rb[:M, :M], P = Rb[M:, :M], R = Rb[M:, M:] +
+ * diagonal_loading (Re tr R / L) I (taps > 0), G = R^-1 P through R = U^H U (Cholesky) and the Schur
+ * complement Sigma = C - P^H G (Sigma = C with taps = 0).  ssspy_update_by_ip1 on the demixing rows
+ * Q = W[..., :M] with Sigma as the weighted covariances is the row update; ssspy_conviva_compose forms
+ * the convolutional filters from its result and ssspy_wpd_apply the estimate.  One workgroup per
+ * (mixture, bin, source); every sum is formed in frame order by one thread: no fp64 atomics, the same
+ * bits on every run and on both routes.  2 <= M <= 8, taps >= 0 and (taps + 1) M <= 64, else
+ * SSSPY_ERR_UNSUPPORTED; delay >= 1 else SSSPY_ERR_BADARG.  (Added at SSSPY_ABI_VERSION 11 without a
+ * bump, as the WPD entry points were: no existing argument list changed.) */
+enum {
+  SSSPY_CONVIVA_ROUTE_AUTO = 0,
+  SSSPY_CONVIVA_ROUTE_RESIDENT = 1,  /* the M x T slab of the bin stays in LDS for the launch */
+  SSSPY_CONVIVA_ROUTE_STREAMING = 2, /* the slab is re-read from memory in tiles              */
+};
+enum {
+  SSSPY_CONVIVA_MIN_CHANNELS = 2,
+  SSSPY_CONVIVA_MAX_CHANNELS = 8,
+  SSSPY_CONVIVA_MAX_ORDER = 64, /* (taps + 1) * n_channels */
+};
+
+/* SSSPY_CONVIVA_ROUTE_RESIDENT (16 M (T + max(taps - 1, 0)) <= 48 KiB) or _STREAMING for a shape (-1:
+ * a shape the kernel does not take); lds_bytes (may be NULL) receives the dynamic LDS of a workgroup
+ * on that route. */
+int ssspy_conviva_route(int B, int M, int F, int T, int taps, int *lds_bytes);
+
+/* Sigma (B, F, M, M, M), full Hermitian with an exactly real diagonal, and G (B, F, M, L, M) (may be
+ * NULL with taps = 0) of every (mixture, bin, source).  failed (B, F, M) int32, zeroed by the caller
+ * once per run: bit 0 is set by a launch in which the triple met a Cholesky pivot that is not positive
+ * and finite and cleared by one in which it did not, bit 1 stays set from the first such launch on;
+ * info[0] (may be NULL) is bumped when bit 1 is set: once per triple and run.  Sigma and G of a triple
+ * that failed are not written.  Rb_out (B, F, M, Lb, Lb), full Hermitian with the loading, and U_out
+ * (B, F, M, L, L), upper triangular with zeros below the diagonal, may each be NULL.  `route`:
+ * SSSPY_CONVIVA_ROUTE_AUTO, or _STREAMING to re-read the slab where it would fit in LDS. */
+int ssspy_conviva_statistics(const void *X, const double *phi, void *Sigma, void *G, int B, int M,
+                             int F, int T, int taps, int delay, double diagonal_loading, int *info,
+                             int *failed, void *Rb_out, void *U_out, int route, void *stream);
+
+/* W (B, F, M, Lb) from the demixing rows Q (B, F, M, M) and G: wb = [q; -G q] with q the conjugated
+ * row, stored conjugated: W[:M] = Q row, W[M + l] = -sum_m conj(G[l][m]) Q[m].  The row of a triple
+ * with bit 0 of `failed` (may be NULL) set is not touched. */
+int ssspy_conviva_compose(const void *Q, const void *G, void *W, const int *failed, int B, int M,
+                          int F, int taps, void *stream);
+
 /* ------------------------------------------------------------------ STFT / ISTFT
  * The transforms the reference's workflow takes from SciPy either side of a separator
  * (tests/package/bss/test_ilrma.py, test_iva.py, test_mnmf.py: scipy.signal.stft(x, window="hann",

@@ -52,6 +52,7 @@ def _units():
         ("wpe.hip", "wpe.o", []),
         ("beamform.hip", "beamform.o", []),
         ("wpd.hip", "wpd.o", []),
+        ("conviva.hip", "conviva.o", []),
         ("ica.hip", "ica.o", []),
         ("pdsbss.hip", "pdsbss.o", []),
         ("hva.hip", "hva.o", []),

@@ -57,6 +57,10 @@ BEAMFORM_MAX_CHANNELS, BEAMFORM_MAX_SOURCES = 8, 16
 # ((taps + 1) * n_channels <= WPD_MAX_ORDER)
 WPD_ROUTE_AUTO, WPD_ROUTE_RESIDENT, WPD_ROUTE_STREAMING = range(3)
 WPD_MAX_CHANNELS, WPD_MAX_ORDER, WPD_MAX_SOURCES = 8, 64, 16
+# SSSPY_CONVIVA_ROUTE_*: `route` of ssspy_conviva_statistics and what ssspy_conviva_route returns; the
+# limits ((taps + 1) * n_channels <= CONVIVA_MAX_ORDER)
+CONVIVA_ROUTE_AUTO, CONVIVA_ROUTE_RESIDENT, CONVIVA_ROUTE_STREAMING = range(3)
+CONVIVA_MIN_CHANNELS, CONVIVA_MAX_CHANNELS, CONVIVA_MAX_ORDER = 2, 8, 64
 # SSSPY_ICA_*: `kind`, `right` of ssspy_ica_stats and `algorithm` of ssspy_ica_step
 ICA_LAPLACE, ICA_LOGISTIC, ICA_LOGCOSH, ICA_IDENTITY, ICA_GIVEN = range(5)
 ICA_RIGHT_Y, ICA_RIGHT_X = range(2)
@@ -188,6 +192,10 @@ PROTOTYPES = {
     "ssspy_wpd_step": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _d, _i, _d, _p, _p,
                             _p, _p, _i, _p]),
     "ssspy_wpd_apply": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _d, _p, _q, _i, _p]),
+    "ssspy_conviva_route": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]),
+    "ssspy_conviva_statistics": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _d, _p, _p, _p, _p, _i,
+                                      _p]),
+    "ssspy_conviva_compose": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "ssspy_ica_chunk_samples": (_i, [_i, _q]),
     "ssspy_ica_workspace_bytes": (_z, [_i, _i, _q]),
     "ssspy_ica_stats": (_i, [_p, _p, _p, _p, _p, _z, _i, _i, _q, _i, _i, _p]),

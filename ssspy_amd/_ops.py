@@ -1058,6 +1058,61 @@ def wpd_apply(X, W, taps, delay, flooring=(_lib.FLOOR_NONE, 0.0), Y=None, loss_d
     return Y
 
 
+# ------------------------------------------------------------------------------- ConvIVA
+def conviva_route(B, M, F, T, taps):
+    """(_lib.CONVIVA_ROUTE_RESIDENT or _STREAMING, dynamic LDS bytes of a workgroup).  Host only."""
+    import ctypes
+
+    lds = ctypes.c_int(0)
+    route = int(_L().ssspy_conviva_route(B, M, F, T, int(taps), ctypes.byref(lds)))
+    if route < 0:
+        raise ValueError("conviva_route: a shape the ConvIVA kernel does not take")
+    return route, lds.value
+
+
+def conviva_statistics(X, phi, taps, delay, diagonal_loading, info, want_statistics=False, Sigma=None,
+                       G=None, failed=None):
+    """The Schur complements Sigma (B, F, M, M, M) and the prediction filters G (B, F, M, taps M, M)
+    of every (mixture, bin, source) from the mixture X (B, M, F, T) and the weights phi (B, M, T);
+    ``failed`` (B, F, M) int32 as ssspy_conviva_statistics keeps it (fresh zeros when not given).
+    Returns (Sigma, G, failed), with ``want_statistics`` (Sigma, G, failed, Rb (B, F, M, Lb, Lb),
+    U (B, F, M, L, L))."""
+    B, M, F, T = X.shape
+    K = int(taps)
+    L, Lb = K * M, (K + 1) * M
+    assert tuple(phi.shape) == (B, M, T) and phi.dtype == dv.f64
+    if Sigma is None:
+        Sigma = dv.zeros((B, F, M, M, M), dv.c128, X.device)
+    if G is None:
+        G = dv.zeros((B, F, M, L, M), dv.c128, X.device)
+    if failed is None:
+        failed = dv.zeros((B, F, M), dv.i32, X.device)
+    Rb = U = None
+    if want_statistics:
+        Rb = dv.zeros((B, F, M, Lb, Lb), dv.c128, X.device)
+        U = dv.zeros((B, F, M, L, L), dv.c128, X.device)
+    route = (_lib.CONVIVA_ROUTE_STREAMING if _routes.get("conviva_resident") is False
+             else _lib.CONVIVA_ROUTE_AUTO)
+    _lib.check(
+        _L().ssspy_conviva_statistics(ptr(X), ptr(phi), ptr(Sigma), ptr(G) if L else None, B, M, F, T,
+                                      K, int(delay), float(diagonal_loading), ptr(info), ptr(failed),
+                                      ptr(Rb), ptr(U) if L else None, route, _st()),
+        "conviva_statistics",
+    )
+    return (Sigma, G, failed, Rb, U) if want_statistics else (Sigma, G, failed)
+
+
+def conviva_compose(Q, G, W, taps, failed=None):
+    """W (B, F, M, (taps + 1) M) from the demixing rows Q (B, F, M, M) and G (B, F, M, taps M, M);
+    rows of triples whose ``failed`` word has bit 0 set stay as they are."""
+    B, F, M, _ = Q.shape
+    K = int(taps)
+    assert tuple(W.shape) == (B, F, M, (K + 1) * M) and tuple(G.shape) == (B, F, M, K * M, M)
+    _lib.check(_L().ssspy_conviva_compose(ptr(Q), ptr(G) if K else None, ptr(W), ptr(failed), B, M, F,
+                                          K, _st()), "conviva_compose")
+    return W
+
+
 # ------------------------------------------------------------------------------ time-domain ICA
 def ica_chunk_samples(N, T):
     """Samples per partial record of the statistics pass (a function of the shape only)."""

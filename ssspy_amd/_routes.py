@@ -44,6 +44,9 @@ _DEFAULTS = {
     # WPD keeps the slab of a bin in LDS where ssspy_wpd_route puts it there; False: every walk
     # re-reads it in tiles (what longer frame axes run)
     "wpd_resident": True,
+    # ConvIVA's statistics kernel keeps the slab of a bin in LDS where ssspy_conviva_route puts it
+    # there; False: the walk re-reads it in tiles (what longer frame axes run)
+    "conviva_resident": True,
 }
 VALUES = dict(_DEFAULTS)  # (tests: monkeypatch.setitem(_routes.VALUES, "implied_filter", False))
 

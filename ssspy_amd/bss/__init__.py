@@ -1,7 +1,9 @@
-from . import admmbss, base, cacgmm, fdica, hva, ica, ilrma, ipsdta, iva, mnmf, overiva, pdsbss, proxbss
+from . import (admmbss, base, cacgmm, conviva, fdica, hva, ica, ilrma, ipsdta, iva, mnmf, overiva,
+               pdsbss, proxbss)
 from .admmbss import ADMMBSS, ADMMBSSBase, MaskingADMMBSS
 from .base import IterativeMethodBase
 from .cacgmm import CACGMM, CACGMMBase
+from .conviva import ConvGaussIVA, ConvIVABase, ConvLaplaceIVA
 from .fdica import (
     AuxFDICA,
     AuxLaplaceFDICA,
@@ -24,5 +26,6 @@ __all__ = ["IterativeMethodBase", "CACGMM", "CACGMMBase", "IPSDTABase", "BlockDe
            "AuxFDICA", "GradLaplaceFDICA", "NaturalGradLaplaceFDICA", "AuxLaplaceFDICA",
            "ProxBSSBase", "PDSBSSBase", "PDSBSS", "MaskingPDSBSS", "MaskingPDSHVA", "HVA", "ADMMBSSBase", "ADMMBSS",
            "MaskingADMMBSS", "MaskingADMMHVA", "GradICA", "NaturalGradICA", "FastICA", "GradLaplaceICA",
-           "NaturalGradLaplaceICA", "OverIVABase", "OverLaplaceIVA", "OverGaussIVA", "admmbss", "base", "cacgmm",
-           "fdica", "hva", "ica", "ilrma", "ipsdta", "iva", "mnmf", "overiva", "pdsbss", "proxbss"]
+           "NaturalGradLaplaceICA", "OverIVABase", "OverLaplaceIVA", "OverGaussIVA", "ConvIVABase",
+           "ConvLaplaceIVA", "ConvGaussIVA", "admmbss", "base", "cacgmm", "conviva", "fdica", "hva",
+           "ica", "ilrma", "ipsdta", "iva", "mnmf", "overiva", "pdsbss", "proxbss"]
