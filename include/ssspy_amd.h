@@ -1757,6 +1757,39 @@ int ssspy_conviva_statistics(const void *X, const double *phi, void *Sigma, void
                              int F, int T, int taps, int delay, double diagonal_loading, int *info,
                              int *failed, void *Rb_out, void *U_out, int route, void *stream);
 
+/* The same statistics with the weights of the ILRMA source model (ILRMA with joint dereverberation,
+ * ILRMA-T of Ikeshita et al.), which depend on the bin: phi_nft = (sum_k basis[b, n, f, k]
+ * activation[b, n, k, t])^(-2 / domain), basis (B, M, F, n_basis) and activation (B, M, n_basis, T)
+ * float64, N = M.  The workgroup of a (mixture, bin, source) forms the weights of every tile of frames
+ * itself where ssspy_conviva_statistics copies phi: one thread per frame sums over k in ascending order,
+ * then 1 / s with domain = 2 (no pow) and pow(s, -2 / domain) otherwise; the basis row is staged once in
+ * LDS (n_basis doubles on top of what ssspy_conviva_route reports), the activation is read coalesced
+ * along t.  The weights are not floored (the reference's varphi = 1 / R is not): a sum of zero gives
+ * phi = inf, R is not finite and the triple takes the failure path.  Everything behind the weights is
+ * the kernel body of ssspy_conviva_statistics, and so are Sigma, G, info, failed, Rb_out, U_out, route
+ * and the limits on M and taps; no atomics, the same bits on every run, on both routes, in a batch or
+ * alone.  phi_out (B, M, F, T) float64 (tests; may be NULL) receives the weights.  1 <= n_basis <=
+ * SSSPY_CONVIVA_MAX_BASIS else SSSPY_ERR_UNSUPPORTED; domain outside (0, 2] or delay < 1:
+ * SSSPY_ERR_BADARG.  (Added at SSSPY_ABI_VERSION 11 without a bump: no existing argument list
+ * changed.) */
+enum { SSSPY_CONVIVA_MAX_BASIS = 32 };
+int ssspy_conviva_statistics_nmf(const void *X, const double *basis, const double *activation,
+                                 void *Sigma, void *G, int B, int M, int F, int T, int taps,
+                                 int delay, int n_basis, double domain, double diagonal_loading,
+                                 int *info, int *failed, void *Rb_out, void *U_out, double *phi_out,
+                                 int route, void *stream);
+
+/* Power normalisation of that model on the convolutional state: psi_n = floor(sqrt(mean_{f,t}
+ * |y_nft|^2)) from Y (B, M, F, T); Y[n] /= psi_n, W[:, n, :] /= psi_n on all (taps + 1) M entries of
+ * the row (W (B, F, M, Lb)) and basis[n] /= psi_n^domain.  Y and W take the same psi, so Y stays W xb
+ * to one rounding per entry; G and the loss do not change.  workspace: one double per (mixture,
+ * source, 16 bin rows), added in order (no atomics).
+ * replaces: ssspy/bss/ilrma.py:365-444 (normalize_by_power) on a state the reference does not have. */
+size_t ssspy_convilrma_normalize_workspace_bytes(int B, int M, int F);
+int ssspy_convilrma_normalize(void *Y, void *W, double *basis, int B, int M, int F, int T, int taps,
+                              int n_basis, double domain, int floor_kind, double floor_eps,
+                              void *workspace, size_t workspace_bytes, void *stream);
+
 /* W (B, F, M, Lb) from the demixing rows Q (B, F, M, M) and G: wb = [q; -G q] with q the conjugated
  * row, stored conjugated: W[:M] = Q row, W[M + l] = -sum_m conj(G[l][m]) Q[m].  The row of a triple
  * with bit 0 of `failed` (may be NULL) set is not touched. */

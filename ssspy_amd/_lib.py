@@ -61,6 +61,7 @@ WPD_MAX_CHANNELS, WPD_MAX_ORDER, WPD_MAX_SOURCES = 8, 64, 16
 # limits ((taps + 1) * n_channels <= CONVIVA_MAX_ORDER)
 CONVIVA_ROUTE_AUTO, CONVIVA_ROUTE_RESIDENT, CONVIVA_ROUTE_STREAMING = range(3)
 CONVIVA_MIN_CHANNELS, CONVIVA_MAX_CHANNELS, CONVIVA_MAX_ORDER = 2, 8, 64
+CONVIVA_MAX_BASIS = 32  # n_basis of ssspy_conviva_statistics_nmf
 # SSSPY_ICA_*: `kind`, `right` of ssspy_ica_stats and `algorithm` of ssspy_ica_step
 ICA_LAPLACE, ICA_LOGISTIC, ICA_LOGCOSH, ICA_IDENTITY, ICA_GIVEN = range(5)
 ICA_RIGHT_Y, ICA_RIGHT_X = range(2)
@@ -195,6 +196,10 @@ PROTOTYPES = {
     "ssspy_conviva_route": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]),
     "ssspy_conviva_statistics": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _d, _p, _p, _p, _p, _i,
                                       _p]),
+    "ssspy_conviva_statistics_nmf": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _d, _p,
+                                          _p, _p, _p, _p, _i, _p]),
+    "ssspy_convilrma_normalize_workspace_bytes": (_z, [_i, _i, _i]),
+    "ssspy_convilrma_normalize": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _d, _i, _d, _p, _z, _p]),
     "ssspy_conviva_compose": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "ssspy_ica_chunk_samples": (_i, [_i, _q]),
     "ssspy_ica_workspace_bytes": (_z, [_i, _i, _q]),

@@ -1102,6 +1102,56 @@ def conviva_statistics(X, phi, taps, delay, diagonal_loading, info, want_statist
     return (Sigma, G, failed, Rb, U) if want_statistics else (Sigma, G, failed)
 
 
+def conviva_statistics_nmf(X, basis, activation, domain, taps, delay, diagonal_loading, info,
+                           want_statistics=False, Sigma=None, G=None, failed=None):
+    """conviva_statistics with the weights of the ILRMA source model, formed in the kernel from basis
+    (B, M, F, n_basis) and activation (B, M, n_basis, T): phi = (basis activation)^(-2 / domain).
+    Returns (Sigma, G, failed), with ``want_statistics`` (Sigma, G, failed, Rb, U, phi (B, M, F, T))."""
+    B, M, F, T = X.shape
+    K = int(taps)
+    L, Lb = K * M, (K + 1) * M
+    Kb = basis.shape[-1]
+    assert tuple(basis.shape) == (B, M, F, Kb) and basis.dtype == dv.f64
+    assert tuple(activation.shape) == (B, M, Kb, T) and activation.dtype == dv.f64
+    if Sigma is None:
+        Sigma = dv.zeros((B, F, M, M, M), dv.c128, X.device)
+    if G is None:
+        G = dv.zeros((B, F, M, L, M), dv.c128, X.device)
+    if failed is None:
+        failed = dv.zeros((B, F, M), dv.i32, X.device)
+    Rb = U = phi = None
+    if want_statistics:
+        Rb = dv.zeros((B, F, M, Lb, Lb), dv.c128, X.device)
+        U = dv.zeros((B, F, M, L, L), dv.c128, X.device)
+        phi = dv.zeros((B, M, F, T), dv.f64, X.device)
+    route = (_lib.CONVIVA_ROUTE_STREAMING if _routes.get("conviva_resident") is False
+             else _lib.CONVIVA_ROUTE_AUTO)
+    _lib.check(
+        _L().ssspy_conviva_statistics_nmf(ptr(X), ptr(basis), ptr(activation), ptr(Sigma),
+                                          ptr(G) if L else None, B, M, F, T, K, int(delay), int(Kb),
+                                          float(domain), float(diagonal_loading), ptr(info),
+                                          ptr(failed), ptr(Rb), ptr(U) if L else None, ptr(phi),
+                                          route, _st()),
+        "conviva_statistics_nmf",
+    )
+    return (Sigma, G, failed, Rb, U, phi) if want_statistics else (Sigma, G, failed)
+
+
+def convilrma_normalize(Y, W, basis, taps, domain, flooring):
+    """Y (B, M, F, T), the rows of W (B, F, M, (taps + 1) M) and basis (B, M, F, n_basis) divided by
+    psi_n = floor(sqrt(mean |y_n|^2)) (the basis by psi_n^domain), in place."""
+    B, M, F, T = Y.shape
+    K = int(taps)
+    assert tuple(W.shape) == (B, F, M, (K + 1) * M) and tuple(basis.shape[:3]) == (B, M, F)
+    ws, ws_bytes = _scratch(_L().ssspy_convilrma_normalize_workspace_bytes(B, M, F), Y.device)
+    _lib.check(
+        _L().ssspy_convilrma_normalize(ptr(Y), ptr(W), ptr(basis), B, M, F, T, K, basis.shape[-1],
+                                       float(domain), flooring[0], flooring[1], ptr(ws), ws_bytes,
+                                       _st()),
+        "convilrma_normalize",
+    )
+
+
 def conviva_compose(Q, G, W, taps, failed=None):
     """W (B, F, M, (taps + 1) M) from the demixing rows Q (B, F, M, M) and G (B, F, M, taps M, M);
     rows of triples whose ``failed`` word has bit 0 set stay as they are."""

@@ -1,8 +1,9 @@
-from . import (admmbss, base, cacgmm, conviva, fdica, hva, ica, ilrma, ipsdta, iva, mnmf, overiva,
-               pdsbss, proxbss)
+from . import (admmbss, base, cacgmm, convilrma, conviva, fdica, hva, ica, ilrma, ipsdta, iva, mnmf,
+               overiva, pdsbss, proxbss)
 from .admmbss import ADMMBSS, ADMMBSSBase, MaskingADMMBSS
 from .base import IterativeMethodBase
 from .cacgmm import CACGMM, CACGMMBase
+from .convilrma import ConvGaussILRMA
 from .conviva import ConvGaussIVA, ConvIVABase, ConvLaplaceIVA
 from .fdica import (
     AuxFDICA,
@@ -27,5 +28,6 @@ __all__ = ["IterativeMethodBase", "CACGMM", "CACGMMBase", "IPSDTABase", "BlockDe
            "ProxBSSBase", "PDSBSSBase", "PDSBSS", "MaskingPDSBSS", "MaskingPDSHVA", "HVA", "ADMMBSSBase", "ADMMBSS",
            "MaskingADMMBSS", "MaskingADMMHVA", "GradICA", "NaturalGradICA", "FastICA", "GradLaplaceICA",
            "NaturalGradLaplaceICA", "OverIVABase", "OverLaplaceIVA", "OverGaussIVA", "ConvIVABase",
-           "ConvLaplaceIVA", "ConvGaussIVA", "admmbss", "base", "cacgmm", "conviva", "fdica", "hva",
+           "ConvLaplaceIVA", "ConvGaussIVA", "ConvGaussILRMA", "admmbss", "base", "cacgmm", "convilrma",
+           "conviva", "fdica", "hva",
            "ica", "ilrma", "ipsdta", "iva", "mnmf", "overiva", "pdsbss", "proxbss"]

@@ -15,6 +15,9 @@
 // of the current estimate.  Sigma goes to ssspy_update_by_ip1 as the weighted covariance of the
 // source; ssspy_conviva_compose then forms the convolutional filter wb = [q; -G q] from the demixing
 // row and stores it conjugated, W[l] = conj(wb[l]), so that ssspy_wpd_apply forms y = W xb.
+// ILRMA with joint dereverberation (ILRMA-T) takes the same statistics with weights that depend on
+// the bin, phi_nft = (T V)_nft^(-2/p), formed inside the kernel (ssspy_conviva_statistics_nmf), and
+// adds the power normalisation of the convolutional state (ssspy_convilrma_normalize).
 //
 // The frame walk is that of csrc/wpd.hip (the structure is copied, not shared: wpd.hip interleaves
 // its power pass and the sums of Phi_s with the walk): tiles of CONVIVA_TILE frames,
@@ -78,10 +81,29 @@ static bool conviva_resident(int M, int K, int T) {
 //   is bumped when bit 1 is set for the first time: once per triple and call.
 //   Rb_out (B, F, M, Lb, Lb) (full Hermitian, loading included), U_out (B, F, M, L, L) (upper
 //   triangular, zeros below the diagonal): tests; each may be NULL.
-template <int NPT, bool RESIDENT>
+//
+// The weights of a tile come from one of two sources, a compile-time choice of the one body:
+//   NMF = false  phi (B, N, T), one weight per (source, frame): IVA.  `nmf` is not read.
+//   NMF = true   phi_nft = (sum_k basis[b,n,f,k] activation[b,n,k,t])^(-2/domain), formed by the
+//                workgroup itself for the tile, one thread per frame, k ascending (1 / s with domain
+//                = 2: no pow); the basis row of the (b, n, f) is staged once in LDS behind the slab,
+//                the activation is read coalesced along t: ILRMA.  `phi` is not read.  Not floored: a
+//                sum of zero gives phi = inf, R is not finite and the pivot check fails the triple.
+// The frame-weight instantiations keep the argument list they had in front of `nmf` and compile to
+// the instructions they compiled to before there was a second source.
+struct NmfWeights {
+  const double *basis;       // (B, N, F, Kb)
+  const double *activation;  // (B, N, Kb, T)
+  double *phi_out;           // (B, N, F, T) or NULL: tests
+  double domain;
+  int Kb;
+};
+
+template <int NPT, bool RESIDENT, bool NMF>
 __global__ __launch_bounds__(CONVIVA_THREADS) void k_conviva(
     const c128 *__restrict__ X, const double *__restrict__ phi, c128 *Sigma, c128 *G, int B, int M,
-    int F, int T, int K, int D, double loading, int *info, int *failed, c128 *Rb_out, c128 *U_out) {
+    int F, int T, int K, int D, double loading, int *info, int *failed, c128 *Rb_out, c128 *U_out,
+    const NmfWeights nmf) {
   extern __shared__ c128 lds[];
   const int tid = threadIdx.x;
   const int N = M;
@@ -104,7 +126,16 @@ __global__ __launch_bounds__(CONVIVA_THREADS) void k_conviva(
   const long long row_stride = (long long)F * T;
   const c128 *__restrict__ Xb = X + ((long long)b * M * F + f) * T;  // row m at Xb + m * row_stride
   const long long bfn = ((long long)b * F + f) * N + n;
-  const double *__restrict__ prow = phi + ((long long)b * N + n) * T;
+  const double *__restrict__ prow = NMF ? nullptr : phi + ((long long)b * N + n) * T;
+  // NMF = true: the activation of (b, n), (Kb, T); the basis row in LDS; phi_out of (b, n, f)
+  const double *__restrict__ arow = nullptr;
+  double *bs = nullptr, *pout = nullptr;
+  if constexpr (NMF) {
+    bs = reinterpret_cast<double *>(slab + (size_t)M * (RESIDENT ? HS : HS + CS));
+    arow = nmf.activation + ((long long)b * N + n) * nmf.Kb * T;
+    if (nmf.phi_out) pout = nmf.phi_out + (((long long)b * N + n) * F + f) * T;
+    if (tid < nmf.Kb) bs[tid] = nmf.basis[(((long long)b * N + n) * F + f) * nmf.Kb + tid];
+  }
 
   if (RESIDENT) {
     for (int m = 0; m < M; ++m) {
@@ -154,7 +185,18 @@ __global__ __launch_bounds__(CONVIVA_THREADS) void k_conviva(
       }
       Hb = Hs + pad;
     }
-    if (tid < nt) wgt[tid] = prow[t0 + tid];
+    if constexpr (NMF) {
+      // (bs was written before the barrier that follows the entry table)
+      if (tid < nt) {
+        double sum = 0.0;
+        for (int k = 0; k < nmf.Kb; ++k) sum += bs[k] * arow[(long long)k * T + t0 + tid];
+        const double w = nmf.domain == 2.0 ? 1.0 / sum : pow(sum, -2.0 / nmf.domain);
+        wgt[tid] = w;
+        if (pout) pout[t0 + tid] = w;
+      }
+    } else {
+      if (tid < nt) wgt[tid] = prow[t0 + tid];
+    }
     __syncthreads();
     // ---- sums: frames in order inside every thread; the frames before D have no history
     const int head = min(nt, max(0, D - t0));
@@ -333,27 +375,74 @@ __global__ __launch_bounds__(256) void k_conviva_compose(const c128 *__restrict_
   W[e] = v;
 }
 
-template <int NPT, bool RESIDENT>
-static int launch_conviva_as(const c128 *X, const double *phi, c128 *Sigma, c128 *G, int B, int M,
-                             int F, int T, int K, int D, double loading, int *info, int *failed,
-                             c128 *Rb, c128 *U, hipStream_t st) {
+// ---- power normalisation of the ILRMA source model: psi_n = floor(sqrt(mean_{f,t} |y_nft|^2)); the
+// estimate, the whole row of the convolutional filter (all Lb entries) and the basis take the same
+// psi, so Y stays W xb to one rounding per entry.
+// acc[(b N + n) slots + s] = sum of |y|^2 over CONVILRMA_POWER_BINS bin rows (one contiguous run):
+// one slot per block, added in slot order by the consumer: no atomics
+constexpr int CONVILRMA_POWER_BINS = 16;
+
+__global__ __launch_bounds__(256) void k_convilrma_power(const c128 *__restrict__ Y, double *acc,
+                                                         int N, int F, int T) {
+  __shared__ double scratch[4];
+  const int n = blockIdx.y, b = blockIdx.z;
+  const int f0 = blockIdx.x * CONVILRMA_POWER_BINS;
+  const long long len = (long long)min(CONVILRMA_POWER_BINS, F - f0) * T;
+  const c128 *run = Y + (((long long)b * N + n) * F + f0) * T;
+  double local = 0.0;
+  for (long long e = threadIdx.x; e < len; e += blockDim.x) local += cabs2(run[e]);
+  const double total = block_sum(local, scratch);
+  if (threadIdx.x == 0) acc[((long long)b * N + n) * gridDim.x + blockIdx.x] = total;
+}
+
+// grid: (F, N, B).  Y (B, N, F, T) /= psi, W (B, F, N, Lb) /= psi, basis (B, N, F, Kb) /= psi^p.
+__global__ __launch_bounds__(256) void k_convilrma_scale(c128 *Y, c128 *W, double *basis,
+                                                         const double *__restrict__ acc, int slots,
+                                                         int N, int F, int T, int Lb, int Kb,
+                                                         double p, int floor_kind, double eps) {
+  const int f = blockIdx.x, n = blockIdx.y, b = blockIdx.z;
+  const double *a = acc + ((long long)b * N + n) * slots;
+  double v = 0.0;
+  for (int s = 0; s < slots; ++s) v += a[s];  // (every thread the same sum)
+  const double psi = apply_floor(sqrt(v / ((double)F * (double)T)), floor_kind, eps);
+  c128 *yrow = Y + (((long long)b * N + n) * F + f) * T;
+  for (int t = threadIdx.x; t < T; t += blockDim.x) {
+    const c128 y = yrow[t];
+    yrow[t] = cmake(y.x / psi, y.y / psi);
+  }
+  c128 *wrow = W + (((long long)b * F + f) * N + n) * Lb;
+  for (int l = threadIdx.x; l < Lb; l += blockDim.x) {
+    const c128 w = wrow[l];
+    wrow[l] = cmake(w.x / psi, w.y / psi);
+  }
+  const double pp = p == 2.0 ? psi * psi : pow(psi, p);
+  double *trow = basis + (((long long)b * N + n) * F + f) * Kb;
+  for (int k = threadIdx.x; k < Kb; k += blockDim.x) trow[k] = trow[k] / pp;
+}
+
+// One launch of the statistics kernel; nmf == NULL: the frame weights phi.
+template <int NPT, bool RESIDENT, bool NMF>
+static int launch_conviva_as(const c128 *X, const double *phi, const NmfWeights *nmf, c128 *Sigma,
+                             c128 *G, int B, int M, int F, int T, int K, int D, double loading,
+                             int *info, int *failed, c128 *Rb, c128 *U, hipStream_t st) {
   const ConvivaLds need = conviva_lds(M, K, T, RESIDENT);
-  const size_t smem = need.fixed_bytes + need.slab_bytes;
+  // (NMF: the basis row behind the slab)
+  const size_t smem = need.fixed_bytes + need.slab_bytes + (NMF ? nmf->Kb * sizeof(double) : 0);
   if (smem > 64 * 1024) {
     // (granted once per instantiation and device, not on every launch)
     static size_t granted[64] = {};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
     if (smem > granted[dev]) {
-      hipError_t e = hipFuncSetAttribute((const void *)k_conviva<NPT, RESIDENT>,
+      hipError_t e = hipFuncSetAttribute((const void *)k_conviva<NPT, RESIDENT, NMF>,
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
       if (e != hipSuccess) return fail(SSSPY_ERR_HIP, hipGetErrorString(e));
       granted[dev] = smem;
     }
   }
-  hipLaunchKernelGGL((k_conviva<NPT, RESIDENT>), dim3((unsigned)((long long)F * M), (unsigned)B),
+  hipLaunchKernelGGL((k_conviva<NPT, RESIDENT, NMF>), dim3((unsigned)((long long)F * M), (unsigned)B),
                      dim3(CONVIVA_THREADS), smem, st, X, phi, Sigma, G, B, M, F, T, K, D, loading,
-                     info, failed, Rb, U);
+                     info, failed, Rb, U, NMF ? *nmf : NmfWeights{});
   return check_launch("k_conviva");
 }
 
@@ -370,6 +459,55 @@ static int conviva_check(int B, int M, int F, int T, int K, int D, const char **
     return SSSPY_ERR_UNSUPPORTED;
   }
   return SSSPY_OK;
+}
+
+// Checks and the choice of the instantiation, for either weight source (nmf == NULL: phi).
+template <bool NMF>
+static int conviva_statistics(const void *X, const double *phi, const NmfWeights *nmf, void *Sigma,
+                              void *G, int B, int M, int F, int T, int taps, int delay,
+                              double diagonal_loading, int *info, int *failed, void *Rb_out,
+                              void *U_out, int route, void *stream) {
+  const char *why;
+  const int rc = conviva_check(B, M, F, T, taps, delay, &why);
+  if (rc != SSSPY_OK) return fail(rc, why);
+  const int K = taps;
+  SSSPY_REQUIRE(X && (NMF ? nmf->basis && nmf->activation : phi != nullptr) && Sigma && failed &&
+                    (G || K == 0),
+                "conviva_statistics: bad argument");
+  SSSPY_REQUIRE(diagonal_loading >= 0.0 && diagonal_loading <= 1.79769313486231570815e308,
+                "conviva_statistics: diagonal_loading is finite and >= 0");
+  SSSPY_REQUIRE(route >= SSSPY_CONVIVA_ROUTE_AUTO && route <= SSSPY_CONVIVA_ROUTE_STREAMING,
+                "conviva_statistics: route is one of SSSPY_CONVIVA_ROUTE_*");
+  const bool resident = route != SSSPY_CONVIVA_ROUTE_STREAMING && conviva_resident(M, K, T);
+  const int Lb = (K + 1) * M;
+  const int npt = (Lb * (Lb + 1) / 2 + CONVIVA_THREADS - 1) / CONVIVA_THREADS;
+  const int D = delay < T ? delay : T;  // (no frame has a history from delay = n_frames on)
+#define CONVIVA_CASE(NPT_)                                                                         \
+  case NPT_:                                                                                       \
+    return resident                                                                                \
+               ? launch_conviva_as<NPT_, true, NMF>((const c128 *)X, phi, nmf, (c128 *)Sigma,       \
+                                                    (c128 *)G, B, M, F, T, K, D, diagonal_loading, \
+                                                    info, failed, (c128 *)Rb_out, (c128 *)U_out,   \
+                                                    as_stream(stream))                             \
+               : launch_conviva_as<NPT_, false, NMF>((const c128 *)X, phi, nmf, (c128 *)Sigma,      \
+                                                     (c128 *)G, B, M, F, T, K, D,                  \
+                                                     diagonal_loading, info, failed,               \
+                                                     (c128 *)Rb_out, (c128 *)U_out,                \
+                                                     as_stream(stream))
+  static_assert(CONVIVA_MAX_NPT == 9, "the cases below cover 1..CONVIVA_MAX_NPT entries per thread");
+  switch (npt) {
+    CONVIVA_CASE(1);
+    CONVIVA_CASE(2);
+    CONVIVA_CASE(3);
+    CONVIVA_CASE(4);
+    CONVIVA_CASE(5);
+    CONVIVA_CASE(6);
+    CONVIVA_CASE(7);
+    CONVIVA_CASE(8);
+    CONVIVA_CASE(9);
+  }
+#undef CONVIVA_CASE
+  return fail(SSSPY_ERR_INTERNAL, "conviva_statistics: no kernel for this order");
 }
 
 }  // namespace ssspy
@@ -392,44 +530,47 @@ int ssspy_conviva_route(int B, int M, int F, int T, int taps, int *lds_bytes) {
 int ssspy_conviva_statistics(const void *X, const double *phi, void *Sigma, void *G, int B, int M,
                              int F, int T, int taps, int delay, double diagonal_loading, int *info,
                              int *failed, void *Rb_out, void *U_out, int route, void *stream) {
+  return conviva_statistics<false>(X, phi, nullptr, Sigma, G, B, M, F, T, taps, delay,
+                                   diagonal_loading, info, failed, Rb_out, U_out, route, stream);
+}
+
+int ssspy_conviva_statistics_nmf(const void *X, const double *basis, const double *activation,
+                                 void *Sigma, void *G, int B, int M, int F, int T, int taps,
+                                 int delay, int n_basis, double domain, double diagonal_loading,
+                                 int *info, int *failed, void *Rb_out, void *U_out, double *phi_out,
+                                 int route, void *stream) {
+  SSSPY_REQUIRE(n_basis >= 1, "conviva_statistics_nmf: bad argument");
+  SSSPY_REQUIRE(domain > 0.0 && domain <= 2.0, "conviva_statistics_nmf: domain is in (0, 2]");
+  if (n_basis > SSSPY_CONVIVA_MAX_BASIS)
+    return fail(SSSPY_ERR_UNSUPPORTED, "conviva_statistics_nmf: up to 32 bases");
+  const NmfWeights nmf = {basis, activation, phi_out, domain, n_basis};
+  return conviva_statistics<true>(X, nullptr, &nmf, Sigma, G, B, M, F, T, taps, delay,
+                                  diagonal_loading, info, failed, Rb_out, U_out, route, stream);
+}
+
+size_t ssspy_convilrma_normalize_workspace_bytes(int B, int M, int F) {
+  if (B <= 0 || M <= 0 || F <= 0) return 0;
+  return (size_t)B * M * ((F + CONVILRMA_POWER_BINS - 1) / CONVILRMA_POWER_BINS) * sizeof(double);
+}
+
+int ssspy_convilrma_normalize(void *Y, void *W, double *basis, int B, int M, int F, int T, int taps,
+                              int n_basis, double domain, int floor_kind, double floor_eps,
+                              void *workspace, size_t workspace_bytes, void *stream) {
   const char *why;
-  const int rc = conviva_check(B, M, F, T, taps, delay, &why);
+  const int rc = conviva_check(B, M, F, T, taps, 1, &why);
   if (rc != SSSPY_OK) return fail(rc, why);
-  const int K = taps;
-  SSSPY_REQUIRE(X && phi && Sigma && failed && (G || K == 0), "conviva_statistics: bad argument");
-  SSSPY_REQUIRE(diagonal_loading >= 0.0 && diagonal_loading <= 1.79769313486231570815e308,
-                "conviva_statistics: diagonal_loading is finite and >= 0");
-  SSSPY_REQUIRE(route >= SSSPY_CONVIVA_ROUTE_AUTO && route <= SSSPY_CONVIVA_ROUTE_STREAMING,
-                "conviva_statistics: route is one of SSSPY_CONVIVA_ROUTE_*");
-  const bool resident = route != SSSPY_CONVIVA_ROUTE_STREAMING && conviva_resident(M, K, T);
-  const int Lb = (K + 1) * M;
-  const int npt = (Lb * (Lb + 1) / 2 + CONVIVA_THREADS - 1) / CONVIVA_THREADS;
-  const int D = delay < T ? delay : T;  // (no frame has a history from delay = n_frames on)
-#define CONVIVA_CASE(NPT_)                                                                         \
-  case NPT_:                                                                                       \
-    return resident ? launch_conviva_as<NPT_, true>((const c128 *)X, phi, (c128 *)Sigma, (c128 *)G, \
-                                                    B, M, F, T, K, D, diagonal_loading, info,      \
-                                                    failed, (c128 *)Rb_out, (c128 *)U_out,         \
-                                                    as_stream(stream))                             \
-                    : launch_conviva_as<NPT_, false>((const c128 *)X, phi, (c128 *)Sigma,          \
-                                                     (c128 *)G, B, M, F, T, K, D,                  \
-                                                     diagonal_loading, info, failed,               \
-                                                     (c128 *)Rb_out, (c128 *)U_out,                \
-                                                     as_stream(stream))
-  static_assert(CONVIVA_MAX_NPT == 9, "the cases below cover 1..CONVIVA_MAX_NPT entries per thread");
-  switch (npt) {
-    CONVIVA_CASE(1);
-    CONVIVA_CASE(2);
-    CONVIVA_CASE(3);
-    CONVIVA_CASE(4);
-    CONVIVA_CASE(5);
-    CONVIVA_CASE(6);
-    CONVIVA_CASE(7);
-    CONVIVA_CASE(8);
-    CONVIVA_CASE(9);
-  }
-#undef CONVIVA_CASE
-  return fail(SSSPY_ERR_INTERNAL, "conviva_statistics: no kernel for this order");
+  SSSPY_REQUIRE(Y && W && basis && n_basis >= 1 && domain > 0.0 && domain <= 2.0,
+                "convilrma_normalize: bad argument");
+  SSSPY_REQUIRE(workspace && workspace_bytes >= ssspy_convilrma_normalize_workspace_bytes(B, M, F),
+                "convilrma_normalize: workspace too small");
+  const int slots = (F + CONVILRMA_POWER_BINS - 1) / CONVILRMA_POWER_BINS;
+  hipStream_t st = as_stream(stream);
+  double *acc = (double *)workspace;
+  hipLaunchKernelGGL(k_convilrma_power, dim3(slots, M, B), dim3(256), 0, st, (const c128 *)Y, acc, M,
+                     F, T);
+  hipLaunchKernelGGL(k_convilrma_scale, dim3(F, M, B), dim3(256), 0, st, (c128 *)Y, (c128 *)W, basis,
+                     acc, slots, M, F, T, (taps + 1) * M, n_basis, domain, floor_kind, floor_eps);
+  return check_launch("k_convilrma_scale");
 }
 
 int ssspy_conviva_compose(const void *Q, const void *G, void *W, const int *failed, int B, int M,
